@@ -11,11 +11,17 @@ the data path: "scaling": "weak").  Steps are replayed from a HIP graph
 capture of the forward; K steps are timed with HIP events on the stream the
 kernel runs on, bracketed by barrier + synchronize, max over ranks.
 
+A plain run sets up, settles and warms up, times the K steps, writes the
+timed path's last logits if ``--dump-outputs DIR`` is given, and prints the
+result line; every leg that takes runs of its own (``per_call``,
+``roofline_gather``, ``cpu_baseline`` / ``parity``) runs under ``--full`` only.
+
 Rank 0 prints one JSON line with the throughput, the roofline of the fused
-kernel (MFMA-bound: its MLP is 98.5 % of the arithmetic) and, at N = 1, the
-host-CPU baseline (oracle/torch_port.py, the reference's op sequence in fp32
-PyTorch-CPU) timed on this machine's cores, with the HIP logits / AUC checked
-against that port on the same batch (``parity``).  ``--config qr|pruned`` runs
+kernel (MFMA-bound: its MLP is 98.5 % of the arithmetic) and, with ``--full``
+at N = 1, the host-CPU baseline (oracle/torch_port.py, the reference's op
+sequence in fp32 PyTorch-CPU) timed on the host's cores, with the HIP logits
+/ AUC checked against that port on the same batch (``parity``).
+``--config qr|pruned`` runs
 BASELINE.json configs[2] / [3] instead of configs[1]; ``--config fwfm`` runs configs[0]'s model (FwFM only,
 no MLP: the HBM-bound gather path) at the Criteo-39 bench size.
 """
@@ -54,11 +60,20 @@ def parse():
     ap.add_argument("--settle-ms", type=float, default=400.0,
                     help="untimed back-to-back forwards for this long before the warmup steps: the chip raises its "
                          "clock over the first ~300 forwards (DESIGN.md section 7); reported in the JSON as 'settle'")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own: per_call, "
+                         "roofline_gather, and (at one GPU) cpu_baseline + parity; without it the run sets up, warms "
+                         "up, times the K steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write DIR/logits.npy (float32): the logits the timed path's last "
+                         "launch on every stream returned, one row per batch of 4096, streams in order (ranks past "
+                         "0 write logits.rank<r>.npy); the same arguments give the same inputs run after run")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
     ap.add_argument("--graph-steps", type=int, default=20, help="forwards captured per hipGraph")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline and parity")
     ap.add_argument("--no-per-call", action="store_true",
-                    help="skip the per_call leg (one forward call per batch, sequential on one stream)")
+                    help="with --full: skip the per_call leg (one forward call per batch, sequential on one stream) "
+                         "and roofline_gather")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="bounded CPU sample per thread count")
     ap.add_argument("--inputs", choices=["uniform", "zipf"], default="uniform")
     ap.add_argument("--table-scale", type=int, default=1,
@@ -398,11 +413,13 @@ def main():
         G = max(1, min(a.graph_steps, max(per_stream(a.steps))))
         graphs = None
         set_pos = [0] * S
+        last_n = [1] * S  # batches of stream k's latest launch (--dump-outputs)
         if M > 1:
             def launch_set(k, n):
                 # n batches (rotating over the resident ones) in one dfwfm_forward_batches launch on stream k
                 i0 = set_pos[k] * S + k
                 set_pos[k] += n
+                last_n[k] = n
                 eng.forward_batches([batches[(i0 + j * S) % n_bufs] for j in range(n)], set_outs[k][:n])
             for k in range(S):
                 with torch.cuda.stream(streams[k]):
@@ -501,6 +518,9 @@ def main():
         torch.cuda.synchronize(dev)
         if os.environ.get("DFWFM_BENCH_IDLE_MS"):  # diagnostics: an idle gap before the timed region
             time.sleep(float(os.environ["DFWFM_BENCH_IDLE_MS"]) / 1e3)
+        # the timed steps start the rotation over the resident batches anew: which batch every step reads does
+        # not depend on how many forwards the (wall-clock bounded) settle ran
+        set_pos[:] = [0] * S
         wall0 = time.perf_counter()
         if gate is not None:
             gate.arm(streams)
@@ -523,6 +543,9 @@ def main():
         wall = time.perf_counter() - wall0
         if world > 1:
             torch.distributed.barrier()
+        if a.dump_outputs:
+            timed = [k for k, n in enumerate(per_stream(a.steps)) if n > 0]  # streams the timed steps ran on
+            dump_outputs(a.dump_outputs, rank, [set_outs[k][:last_n[k]] if M > 1 else [outs[k]] for k in timed])
     # the timed region: the earliest stream start to the latest stream end
     first = min(range(S), key=lambda k: s0[0].elapsed_time(s0[k]))
     last = max(range(S), key=lambda k: s0[0].elapsed_time(s1[k]))
@@ -621,24 +644,35 @@ def main():
                 "us_per_batch": floor_us, "frac": round(floor_us / (ms_per_step * 1e3), 4),
                 "source": "tools/ubench_gather.hip 3 (profiles/r02/r02q_ubench_gather_nb3.log)"}
         result["roofline_mfma"] = mfma
-    if deep and not a.no_per_call and not (a.config == "pruned" and sparse_on):
+    if a.full and deep and not a.no_per_call and not (a.config == "pruned" and sparse_on):
         # north_star: "achieved HBM GB/s on the gather" -- the gather / shallow half as its own launch
         gl = gather_leg(eng, batches, dev, a.steps, bytes_ - 4)
         if world > 1:
             gl["us_per_batch"] = round(max_over_ranks(gl["us_per_batch"], world, dev), 3)
         result["roofline_gather"] = gl
-    if not a.no_per_call and not (a.config == "pruned" and sparse_on):
+    if a.full and not a.no_per_call and not (a.config == "pruned" and sparse_on):
         pc = per_call_leg(eng, batches, dev, a.steps, flops, bytes_, a.config)
         if world > 1:
             pc["us_per_batch"] = round(max_over_ranks(pc["us_per_batch"], world, dev), 3)
             pc["samples_per_s"] = round(world * BATCH / (pc["us_per_batch"] / 1e6), 1)
         result["per_call"] = pc
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         result["cpu_baseline"], result["parity"] = cpu_baseline(cfg, params, sizes, a.cpu_seconds, model, dev)
     if rank == 0:
         print(json.dumps(result), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()
+
+
+def dump_outputs(path, rank, per_stream_logits):
+    """--dump-outputs: what the callers of the timed path's last launches hold when the timed steps are done -- the
+    logits of every batch of the last launch on each stream (a set of batches, or one batch per graph replay / eager
+    call), one float32 row of BATCH per batch, the streams in order.  The timed steps start the rotation over the
+    resident batches anew, so with S streams the j-th batch of stream k's first set is resident batch k + j S (inputs:
+    seed 1000 rank + that index), and so on round the resident batches: the same rows run after run."""
+    rows = [t.detach().to("cpu", torch.float32).numpy() for ts in per_stream_logits for t in ts]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "logits.npy" if rank == 0 else f"logits.rank{rank}.npy"), np.stack(rows))
 
 
 def per_call_leg(eng, batches, dev, steps, flops, bytes_, config, settle_ms=150.0):
