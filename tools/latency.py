@@ -7,7 +7,11 @@ with HIP events around it (device time) and by the host clock around launch + sy
 batch's forward is also replayed from a one-forward hipGraph (launch overhead of a serving loop that captures).
 Prints one JSON line.
 
-  python tools/latency.py [--calls 1000] [--batches 1,16,64,256,1024,4096,8192]
+  python tools/latency.py [--calls 1000] [--batches 1,16,64,256,1024,4096,8192] [--small]
+
+--small: the small-batch serving forward (eng.forward_small, include/dfwfm_serve.h) measured beside eng.forward at
+every batch, same figures, under models["deepfwfm_small"] (the batch where it stops winning is the value to give
+DeepFMs.small_batch_rows).
 """
 import argparse
 import json
@@ -35,26 +39,26 @@ def build(deep, dev):
     return m, sizes
 
 
-def measure(eng, xi, xv, out, calls, dev):
+def measure(fwd, xi, xv, out, calls, dev):
     """median / p99 device time per call (events), median host time per call (launch + synchronize), and the
     median device time of a one-forward graph replay"""
     st = torch.cuda.current_stream(dev)
     for _ in range(20):
-        eng.forward(xi, xv, out)
+        fwd(xi, xv, out)
     torch.cuda.synchronize(dev)
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(calls)]
     host = []
     for e0, e1 in ev:
         t0 = time.perf_counter()
         e0.record(st)
-        eng.forward(xi, xv, out)
+        fwd(xi, xv, out)
         e1.record(st)
         e1.synchronize()
         host.append(time.perf_counter() - t0)
     dev_us = np.array([e0.elapsed_time(e1) * 1e3 for e0, e1 in ev])
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g):
-        eng.forward(xi, xv, out)
+        fwd(xi, xv, out)
     torch.cuda.synchronize(dev)
     ghost = []
     for _ in range(calls):
@@ -67,7 +71,7 @@ def measure(eng, xi, xv, out, calls, dev):
     g20 = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g20):
         for _ in range(20):
-            eng.forward(xi, xv, out)
+            fwd(xi, xv, out)
     reps = max(5, calls // 20)
     for _ in range(reps):
         g20.replay()
@@ -87,6 +91,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=1000)
     ap.add_argument("--batches", default="1,16,64,256,1024,4096,8192")
+    ap.add_argument("--small", action="store_true", help="also measure eng.forward_small (deep model)")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
@@ -96,19 +101,23 @@ def main():
                    "(data/results/criteo.md:5)", "calls": a.calls, "models": {}}
     for name, deep in (("deepfwfm", 1), ("fwfm", 0)):
         m, sizes = build(deep, dev)
-        rows = {}
+        rows, small = {}, {}
         with torch.no_grad():
             eng = m._sync_engine(dev)
             for b in [int(x) for x in a.batches.split(",")]:
                 xi, xv = synth.synth_inputs(sizes, 13, b, seed=7)
                 xi, xv = torch.from_numpy(xi).to(dev), torch.from_numpy(xv).to(dev)
                 out = torch.empty(b, dtype=torch.float32, device=dev)
-                r = measure(eng, xi, xv, out, a.calls if b <= 256 else max(100, a.calls // 10), dev)
-                r["samples_per_s_one_call_at_a_time"] = round(b / (r["device_us_median"] * 1e-6), 1)
-                if deep:  # f32 MFMA fraction of the back-to-back rate (967,620 FLOP per sample, 157.3 TF/s)
-                    r["mfma_frac_back_to_back"] = round(967620 * b / (r["back_to_back_us"] * 1e-6) / 157.3e12, 4)
-                rows[str(b)] = r
+                calls = a.calls if b <= 256 else max(100, a.calls // 10)
+                for fwd, dst in ((eng.forward, rows),) + (((eng.forward_small, small),) if a.small and deep else ()):
+                    r = measure(fwd, xi, xv, out, calls, dev)
+                    r["samples_per_s_one_call_at_a_time"] = round(b / (r["device_us_median"] * 1e-6), 1)
+                    if deep:  # f32 MFMA fraction of the back-to-back rate (967,620 FLOP per sample, 157.3 TF/s)
+                        r["mfma_frac_back_to_back"] = round(967620 * b / (r["back_to_back_us"] * 1e-6) / 157.3e12, 4)
+                    dst[str(b)] = r
         res["models"][name] = rows
+        if small:
+            res["models"][name + "_small"] = small
     print(json.dumps(res))
 
 

@@ -108,6 +108,11 @@ class DeepFMs(nn.Module):
         # first-order weight in one aligned row, dfwfm_model_pack_tables), rebuilt after weight updates; the values
         # are copied, so the logits are the same bits either way
         self.pack_tables = True
+        # a no-grad forward of at most this many rows on a HIP device takes the small-batch serving path
+        # (ForwardEngine.forward_small, include/dfwfm_serve.h: every hidden layer spread over the chip) when the model
+        # has a deep tower; 0 (default): never.  Its logits agree with the default path's to rounding, not bit for bit
+        # (the batch below which it is faster)
+        self.small_batch_rows = 0
         # the device backward's gradient sums in a fixed order (dfwfm_set_deterministic; like
         # torch.use_deterministic_algorithms): two runs of a training step give the same bits, at ~+7 us (+2.6 %) per
         # step at Criteo-39 (sorted table scatter, split-K slices); on by default, False: float atomics (arrival order)
@@ -264,6 +269,7 @@ class DeepFMs(nn.Module):
                 d = self._field_desc(None if second is None else second[f], None if first is None else first[f])
                 tabs.append((d["emb2"], d["emb1"]))
             eng.sync_packed(tabs, self.pack_tables)
+            eng.small_rows = max(int(getattr(self, "small_batch_rows", 0)), 0) if self.use_deep else 0
         return eng
 
     def _sync_cpu_engine(self):

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "dfwfm_internal.h"
+#include "../../include/dfwfm_serve.h"
 
 using namespace dfwfm;
 
@@ -826,6 +827,72 @@ int dfwfm_forward_gather(dfwfm_model* m, const int64_t* xi, int64_t xi_stride, c
   a.part_fs = first_second;
   hipError_t e = launch_forward(a, m->D, 1, 1, 8, m->lds_inf, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, "gather launch");
+  return DFWFM_OK;
+}
+
+// The small-batch serving forward (include/dfwfm_serve.h): the gather / shallow half as dfwfm_forward_gather launches
+// it, into the caller's workspace, then the deep tower one launch per layer (dfwfm_serve.hip).
+int dfwfm_serve_abi_version(void) { return DFWFM_SERVE_ABI_VERSION; }
+
+int dfwfm_serve_workspace_bytes(dfwfm_model* m, int64_t batch, size_t* bytes) {
+  if (!m || !bytes) return fail(DFWFM_ERR_INVALID_ARG, "null argument");
+  if (batch < 0) return fail(DFWFM_ERR_INVALID_ARG, "negative batch");
+  if (!m->cfg.use_deep) return fail(DFWFM_ERR_UNSUPPORTED, "serve forward: the model has no deep tower");
+  *bytes = sizeof(float) * serve_workspace_floats(m->NT, m->NC0, batch);
+  return DFWFM_OK;
+}
+
+int dfwfm_serve_forward(dfwfm_model* m, const int64_t* xi, int64_t xi_stride, const float* xv, int64_t xv_stride,
+                        int64_t batch, float* out, void* workspace, size_t ws_bytes, void* stream) {
+  if (!m) return fail(DFWFM_ERR_INVALID_ARG, "null model");
+  if (!m->cfg.use_deep)
+    return fail(DFWFM_ERR_UNSUPPORTED, "serve forward: the model has no deep tower (dfwfm_forward is one short launch)");
+  int rc = check_inputs(m, xi, xi_stride, xv, xv_stride, batch, out);
+  if (rc != DFWFM_OK || batch == 0) return rc;
+  if (!workspace) return fail(DFWFM_ERR_INVALID_ARG, "null workspace");
+  const size_t need = sizeof(float) * serve_workspace_floats(m->NT, m->NC0, batch);
+  if (ws_bytes < need)
+    return fail(DFWFM_ERR_INVALID_ARG, "workspace of %zu bytes < %zu (dfwfm_serve_workspace_bytes)", ws_bytes, need);
+  if (reinterpret_cast<uintptr_t>(workspace) % 16) return fail(DFWFM_ERR_INVALID_ARG, "workspace not 16-byte aligned");
+  const int64_t tiles = (batch + kBM - 1) / kBM;
+  if (tiles * m->NT > 0x7fffffff) return fail(DFWFM_ERR_UNSUPPORTED, "batch too large for the serve forward");
+  const size_t rows16 = (size_t)tiles * kBM;
+  ServeArgs sa;
+  memset(&sa, 0, sizeof sa);
+  float* w = static_cast<float*>(workspace);
+  float* deep_emb = w;
+  w += rows16 * m->NC0 * 16;
+  float* fs = w;
+  w += rows16;
+  sa.act[0] = w;
+  w += rows16 * m->NT * 16;
+  sa.act[1] = w;
+  w += rows16 * m->NT * 16;
+  sa.partial = w;
+  // the gather launch: the MLP-free forward's kernel storing the E tile and first + second (dfwfm_forward_gather)
+  FwdArgs a;
+  fill_forward_args(m, a, xi, xi_stride, xv, xv_stride, batch, nullptr);
+  a.flags &= ~kHasDeep;
+  if (m->MT <= 3) a.flags |= kP3Pieces;
+  a.part_stride = m->NC0 * 16;
+  a.part_e = deep_emb;
+  a.part_fs = fs;
+  hipError_t e = launch_forward(a, m->D, 1, 1, 8, m->lds_inf, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "serve gather launch");
+  sa.deep_emb = deep_emb;
+  sa.fs = fs;
+  sa.wpack = m->d_wpack;
+  sa.mlp_b = m->d_mlp_b;
+  sa.fc = m->d_fc;
+  sa.bias = m->d_bias;
+  sa.out = out;
+  sa.batch = batch;
+  sa.H = m->H;
+  sa.N = m->N;
+  sa.NT = m->NT;
+  sa.NC0 = m->NC0;
+  e = launch_serve_mlp(sa, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "serve MLP launch");
   return DFWFM_OK;
 }
 

@@ -384,6 +384,25 @@ hipError_t launch_ell_build(const EllArgs& a, int rows, hipStream_t s);
 hipError_t launch_sparse_mlp(const SpMlpArgs& a, hipStream_t s);
 size_t sparse_mlp_lds_bytes(int K0p, int N);
 
+// Small-batch serving forward (dfwfm_serve.hip): the deep tower as one launch per layer, a workgroup per
+// (row tile, output tile), behind the gather launch that wrote deep_emb / fs; every buffer but the model's
+// parameters is in the caller's workspace.
+struct ServeArgs {
+  const float* deep_emb;   // [rows16][NC0*16] E rows of the gather launch (rows >= batch unwritten)
+  const float* fs;         // [rows16] first + second order
+  float* act[2];           // [rows16][NT*16] layer outputs, ping-pong
+  float* partial;          // [rows16][NT] the last layer's per-tile shares of deep[b]
+  const float4* wpack;     // the forward fragments, per layer [NT][NC][64] float4
+  const float* mlp_b;      // [H][NT*16]
+  const float* fc;         // [NT*16]
+  const float* bias;       // [1]
+  float* out;              // [batch] logits
+  int64_t batch;
+  int32_t H, N, NT, NC0;
+};
+size_t serve_workspace_floats(int NT, int NC0, int64_t batch);
+hipError_t launch_serve_mlp(const ServeArgs& a, hipStream_t s);
+
 // dW_l += G_l^T X_{l-1} and db_l += sum_b G_l for every layer in one launch.
 struct DwArgs {
   const float* G[kMaxH + 1];

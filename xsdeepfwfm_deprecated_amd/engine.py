@@ -68,6 +68,9 @@ class ForwardEngine:
         self._tables_key = None
         self._dense_key = None
         self._keep = None  # host-side descriptor array kept alive
+        # forward() takes the small-batch path (forward_small) for 0 < B <= small_rows; 0: never (DeepFMs sets it
+        # from its small_batch_rows for models with a deep tower)
+        self.small_rows = 0
 
     def close(self):
         if self.handle is not None and self.handle.value:
@@ -176,6 +179,8 @@ class ForwardEngine:
     # -- hot path ----------------------------------------------------------
     def forward(self, xi: torch.Tensor, xv: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
         B = xi.shape[0]
+        if 0 < B <= self.small_rows:
+            return self.forward_small(xi, xv, out)
         ncat = self.cfg["field_size"] - self.cfg["numerical"]
         num = self.cfg["numerical"]
         _require_rows(xi, "Xi", torch.int64, self.device, ncat)
@@ -194,6 +199,39 @@ class ForwardEngine:
                                          _stream_handle(self.device))
         _lib.check(rc, "dfwfm_forward")
         return out
+
+    def forward_small(self, xi: torch.Tensor, xv: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+        """dfwfm_serve_forward (include/dfwfm_serve.h): the low-latency forward of a small batch -- the gather launch,
+        then every hidden layer as its own launch with a workgroup per 16 x 16 output tile, so a handful of rows use
+        many CUs instead of one.  Deep models only (DfwfmError otherwise).  Logits agree with forward() to rounding
+        (another fixed summation order); a row's bits do not depend on the batch around it."""
+        B = xi.shape[0]
+        ncat = self.cfg["field_size"] - self.cfg["numerical"]
+        num = self.cfg["numerical"]
+        _require_rows(xi, "Xi", torch.int64, self.device, ncat)
+        _require_rows(xv, "Xv", torch.float32, self.device, num)
+        if out is None:
+            out = torch.empty(B, dtype=torch.float32, device=self.device)
+        xs = xi.stride(0) if ncat > 0 else 0
+        vs = xv.stride(0) if num > 0 else 0
+        ws_bytes = self._serve_ws_bytes(B)
+        # from torch's stream-ordered caching allocator: calls in flight on several streams never share one
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device) if ws_bytes else None
+        rc = _lib.lib().dfwfm_serve_forward(self.handle, ctypes.c_void_p(xi.data_ptr()), xs,
+                                            ctypes.c_void_p(xv.data_ptr()), vs, B,
+                                            ctypes.c_void_p(out.data_ptr()), _ptr(ws), ws_bytes,
+                                            _stream_handle(self.device))
+        _lib.check(rc, "dfwfm_serve_forward")
+        return out
+
+    def _serve_ws_bytes(self, B: int) -> int:
+        cache = self.__dict__.setdefault("_serve_ws_cache", {})  # a function of the model's shape and B alone
+        if B not in cache:
+            n = ctypes.c_size_t(0)
+            _lib.check(_lib.lib().dfwfm_serve_workspace_bytes(self.handle, B, ctypes.byref(n)),
+                       "dfwfm_serve_workspace_bytes")
+            cache[B] = int(n.value)
+        return cache[B]
 
     def forward_batches(self, batches, outs) -> list:
         """dfwfm_forward_batches: the forward of every (xi, xv) in `batches` (same batch size and row strides),
