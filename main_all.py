@@ -17,7 +17,11 @@ from xsdeepfwfm_deprecated_amd.data import get_dataset
 
 
 def main(argv=None):
-    pars = get_parser().parse_args(argv)
+    parser = get_parser()
+    pars = parser.parse_args(argv)
+    if pars.mlp_dtype == "bf16" and not (pars.use_cuda and pars.time_on_cuda and torch.cuda.is_available()):
+        # before any training: the bf16 deep tower is HIP only, and both models (fit's evaluation, the benchmark) use it
+        parser.error("-mlp_dtype bf16 needs -use_cuda 1 -time_on_cuda 1 and a HIP device")
     np.random.seed(pars.random_seed)
     random.seed(pars.random_seed)
     torch.manual_seed(pars.random_seed)

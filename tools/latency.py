@@ -7,11 +7,17 @@ with HIP events around it (device time) and by the host clock around launch + sy
 batch's forward is also replayed from a one-forward hipGraph (launch overhead of a serving loop that captures).
 Prints one JSON line.
 
-  python tools/latency.py [--calls 1000] [--batches 1,16,64,256,1024,4096,8192] [--small]
+  python tools/latency.py [--calls 1000] [--batches 1,16,64,256,1024,4096,8192] [--small] [--bf16]
 
 --small: the small-batch serving forward (eng.forward_small, include/dfwfm_serve.h) measured beside eng.forward at
 every batch, same figures, under models["deepfwfm_small"] (the batch where it stops winning is the value to give
 DeepFMs.small_batch_rows).
+
+--bf16: the forward with a bf16 deep tower (eng.forward_bf16, include/dfwfm_bf16.h) beside eng.forward at every batch,
+same figures, under models["deepfwfm_bf16"], plus bf16_mfma_frac_back_to_back = 952,800 tower FLOP per sample over
+the back-to-back time, as a fraction of 2.5 PF/s.  A batch that is a multiple of 4096 rows and at least 8192 (up to
+81920 = 20 x 4096, the headline's workload) is also timed as one eng.forward_batches call over its 4096-row slices:
+forward_batches_4096_us (per call) and forward_batches_4096_us_per_batch in the f32 row.
 """
 import argparse
 import json
@@ -87,12 +93,33 @@ def measure(fwd, xi, xv, out, calls, dev):
             "back_to_back_us": round(e0.elapsed_time(e1) * 1e3 / (reps * 20), 2)}
 
 
+def measure_batch_set(eng, xi, xv, out, dev, reps=10):
+    """device time of one eng.forward_batches call over the 4096-row slices of (xi, xv), calls issued back to back"""
+    nb = xi.shape[0] // 4096
+    batches = [(xi[i * 4096:(i + 1) * 4096], xv[i * 4096:(i + 1) * 4096]) for i in range(nb)]
+    outs = [out[i * 4096:(i + 1) * 4096] for i in range(nb)]
+    st = torch.cuda.current_stream(dev)
+    for _ in range(5):
+        eng.forward_batches(batches, outs)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(st)
+    for _ in range(reps):
+        eng.forward_batches(batches, outs)
+    e1.record(st)
+    e1.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / reps, nb
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=1000)
     ap.add_argument("--batches", default="1,16,64,256,1024,4096,8192")
     ap.add_argument("--small", action="store_true", help="also measure eng.forward_small (deep model)")
+    ap.add_argument("--bf16", action="store_true", help="also measure eng.forward_bf16 (deep model)")
     a = ap.parse_args()
+    batches = [int(x) for x in a.batches.split(",")]
+    if not batches or min(batches) < 1 or max(batches) > 81920:
+        ap.error("--batches: sizes from 1 to 81920")
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     from xsdeepfwfm_deprecated_amd import synth
@@ -101,21 +128,32 @@ def main():
                    "(data/results/criteo.md:5)", "calls": a.calls, "models": {}}
     for name, deep in (("deepfwfm", 1), ("fwfm", 0)):
         m, sizes = build(deep, dev)
-        rows, small = {}, {}
+        rows, small, bf16 = {}, {}, {}
         with torch.no_grad():
             eng = m._sync_engine(dev)
-            for b in [int(x) for x in a.batches.split(",")]:
+            if a.bf16 and deep:
+                eng.sync_bf16(True)
+            for b in batches:
                 xi, xv = synth.synth_inputs(sizes, 13, b, seed=7)
                 xi, xv = torch.from_numpy(xi).to(dev), torch.from_numpy(xv).to(dev)
                 out = torch.empty(b, dtype=torch.float32, device=dev)
-                calls = a.calls if b <= 256 else max(100, a.calls // 10)
-                for fwd, dst in ((eng.forward, rows),) + (((eng.forward_small, small),) if a.small and deep else ()):
+                calls = a.calls if b <= 256 else (max(100, a.calls // 10) if b <= 8192 else max(40, a.calls // 25))
+                for fwd, dst in ((eng.forward, rows),) + (((eng.forward_small, small),) if a.small and deep else ()) \
+                        + (((eng.forward_bf16, bf16),) if a.bf16 and deep else ()):
                     r = measure(fwd, xi, xv, out, calls, dev)
                     r["samples_per_s_one_call_at_a_time"] = round(b / (r["device_us_median"] * 1e-6), 1)
-                    if deep:  # f32 MFMA fraction of the back-to-back rate (967,620 FLOP per sample, 157.3 TF/s)
+                    if deep and dst is not bf16:  # f32 MFMA fraction of the back-to-back rate (967,620 FLOP per sample, 157.3 TF/s)
                         r["mfma_frac_back_to_back"] = round(967620 * b / (r["back_to_back_us"] * 1e-6) / 157.3e12, 4)
+                    if dst is bf16:  # the tower alone (952,800 FLOP per sample) against the bf16 MFMA peak
+                        r["bf16_mfma_frac_back_to_back"] = round(952800 * b / (r["back_to_back_us"] * 1e-6) / 2.5e15, 4)
                     dst[str(b)] = r
+                if a.bf16 and deep and b >= 8192 and b % 4096 == 0:
+                    t, nb = measure_batch_set(eng, xi, xv, out, dev)
+                    rows[str(b)]["forward_batches_4096_us"] = round(t, 2)
+                    rows[str(b)]["forward_batches_4096_us_per_batch"] = round(t / nb, 2)
         res["models"][name] = rows
+        if bf16:
+            res["models"][name + "_bf16"] = bf16
         if small:
             res["models"][name + "_small"] = small
     print(json.dumps(res))

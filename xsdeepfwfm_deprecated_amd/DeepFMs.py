@@ -113,6 +113,11 @@ class DeepFMs(nn.Module):
         # has a deep tower; 0 (default): never.  Its logits agree with the default path's to rounding, not bit for bit
         # (the batch below which it is faster)
         self.small_batch_rows = 0
+        # precision of the deep tower's hidden layers in a no-grad forward on a HIP device: "f32" (default), or "bf16"
+        # -- bf16 MFMA with f32 accumulation (ForwardEngine.forward_bf16, include/dfwfm_bf16.h: the numeric contract),
+        # the gather, first order and FwFM staying exact f32; it takes precedence over small_batch_rows.  Training is
+        # f32 either way; a model without a deep tower ignores it
+        self.mlp_dtype = "f32"
         # the device backward's gradient sums in a fixed order (dfwfm_set_deterministic; like
         # torch.use_deterministic_algorithms): two runs of a training step give the same bits, at ~+7 us (+2.6 %) per
         # step at Criteo-39 (sorted table scatter, split-K slices); on by default, False: float atomics (arrival order)
@@ -270,7 +275,19 @@ class DeepFMs(nn.Module):
                 tabs.append((d["emb2"], d["emb1"]))
             eng.sync_packed(tabs, self.pack_tables)
             eng.small_rows = max(int(getattr(self, "small_batch_rows", 0)), 0) if self.use_deep else 0
+            eng.bf16 = eng.sync_bf16(self._mlp_bf16()) if self.use_deep else False
         return eng
+
+    def _mlp_bf16(self) -> bool:
+        """Whether mlp_dtype asks for the bf16 deep tower (validated here: at the next forward)."""
+        dt = getattr(self, "mlp_dtype", "f32")
+        if dt not in ("f32", "bf16"):
+            raise ValueError(f"mlp_dtype must be 'f32' or 'bf16', got {dt!r}")
+        if not self.use_deep or dt == "f32":
+            return False
+        if self.sparse_mlp_max_density > 0:
+            raise ValueError("mlp_dtype='bf16' and sparse_mlp_max_density > 0 are two deep towers: choose one")
+        return True
 
     def _sync_cpu_engine(self):
         """The host kernels' engine (libdfwfm_cpu.so), re-described on every call (pointers, no copies)."""
@@ -348,9 +365,12 @@ class DeepFMs(nn.Module):
             from .training import train_forward
             return train_forward(self, eng, xi, xv)
         from . import torch_ops  # torch.ops.dfwfm.forward (the registered custom op)
+        if device.type == "cpu" and self._mlp_bf16():
+            raise DfwfmError("mlp_dtype='bf16' is the HIP-only bf16 MFMA path (include/dfwfm_bf16.h); "
+                             "a CPU model runs mlp_dtype='f32'")
         if device.type != "cpu":  # (the host kernel has no serving copy or pruned-layout variants)
             self._sync_inference(device)  # the tables' serving copy, re-packed after weight updates
-            if self.use_deep:
+            if self.use_deep and not eng.bf16:
                 # magnitude-pruned hidden layers (fit(prune=1), reference :647-673) run as a sparse MLP when
                 # at most sparse_mlp_max_density of their weights are nonzero (checked once per weight update)
                 eng.sync_sparse(self.sparse_mlp_max_density)
@@ -448,7 +468,7 @@ class DeepFMs(nn.Module):
                 # the full batches as batch sets (dfwfm_forward_batches: up to 32 resident batches per launch, the
                 # same logits as one forward each); the sparse-MLP / pair-list variants keep one forward per batch
                 eng = self._sync_inference(dev)
-                alt = eng.sync_sparse(self.sparse_mlp_max_density) if self.use_deep else (
+                alt = (eng.bf16 or eng.sync_sparse(self.sparse_mlp_max_density)) if self.use_deep else (
                     eng.sync_pairs(self.fwfm_pair_max) if self.use_fwfm else False)
                 if not alt:
                     nfull = x_size // bs

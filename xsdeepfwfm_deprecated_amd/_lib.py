@@ -24,7 +24,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libdfwfm.so")
 # A/B of build variants only (e.g. libdfwfm_ns4.so built with DFWFM_HIPCC_FLAGS=-DDFWFM_NSETS=4)
 LOAD_PATH = os.path.join(PKG_DIR, os.environ["DFWFM_LIB"]) if os.environ.get("DFWFM_LIB") else LIB_PATH
 SOURCES = ["dfwfm_kernels.hip", "dfwfm_fwd32.hip", "dfwfm_ftrain.hip", "dfwfm_train.hip", "dfwfm_prune.hip", "dfwfm_metrics.hip", "dfwfm_sparse.hip",
-           "dfwfm_spmlp.hip", "dfwfm_serve.hip", "dfwfm_capi.hip"]
+           "dfwfm_spmlp.hip", "dfwfm_serve.hip", "dfwfm_bf16.hip", "dfwfm_capi.hip"]
 # the forward / backward kernel templates are instantiated once per embedding size, each size in its own
 # translation unit (-DDFWFM_KD=<D>) so they compile in parallel; the plain object holds everything else
 EMB_SIZES = (4, 8, 10, 16, 32)
@@ -38,7 +38,7 @@ def _units():
         u += [(s, f"{os.path.splitext(s)[0]}_d{d}.o", [f"-DDFWFM_KD={d}"]) for d in EMB_SIZES]
     return u
 HEADERS = ["dfwfm_internal.h", "dfwfm_device.h", os.path.join("..", "..", "include", "dfwfm.h"),
-           os.path.join("..", "..", "include", "dfwfm_serve.h")]
+           os.path.join("..", "..", "include", "dfwfm_serve.h"), os.path.join("..", "..", "include", "dfwfm_bf16.h")]
 ARCH = os.environ.get("DFWFM_OFFLOAD_ARCH", "gfx950")
 CPU_PATH = os.path.join(PKG_DIR, "libdfwfm_cpu.so")
 CPU_SOURCES = ["dfwfm_cpu.cpp"]
@@ -160,6 +160,15 @@ SERVE_SIGNATURES = {
     "dfwfm_serve_workspace_bytes": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.POINTER(ctypes.c_size_t)]),
     "dfwfm_serve_forward": (ctypes.c_int, [_P, _P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int64, _P, _P,
                                            ctypes.c_size_t, _P]),
+}
+
+# the forward with a bf16 deep tower (include/dfwfm_bf16.h): same library, its own header and ABI version
+BF16_SIGNATURES = {
+    "dfwfm_bf16_abi_version": (ctypes.c_int, []),
+    "dfwfm_model_pack_bf16": (ctypes.c_int, [_P, ctypes.c_int, _P]),
+    "dfwfm_bf16_workspace_bytes": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.POINTER(ctypes.c_size_t)]),
+    "dfwfm_bf16_forward": (ctypes.c_int, [_P, _P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int64, _P, _P,
+                                          ctypes.c_size_t, _P]),
 }
 
 _lib = None
@@ -361,6 +370,12 @@ def lib():
             fn.argtypes = args
         if L.dfwfm_serve_abi_version() != 1:
             raise DfwfmError("libdfwfm serve ABI mismatch")
+        for name, (res, args) in BF16_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        if L.dfwfm_bf16_abi_version() != 1:
+            raise DfwfmError("libdfwfm bf16 ABI mismatch")
         _lib = L
     return _lib
 

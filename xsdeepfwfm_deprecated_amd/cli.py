@@ -66,6 +66,9 @@ def get_parser():
     a("-twitter_category", default="like", type=str, choices=["reply", "retweet", "retweet_comment", "like"])
     a("-time_on_cuda", default=0, type=int)
     a("-data_root", default=".", type=str, help="directory holding data/ (this engine's addition)")
+    a("-mlp_dtype", default="f32", type=str, choices=["f32", "bf16"],
+      help="deep tower of the inference forward: f32, or bf16 MFMA with f32 accumulation (HIP only; this "
+           "engine's addition, DeepFMs.mlp_dtype)")
     return p
 
 
@@ -102,14 +105,16 @@ def load_model_dic(model, model_file, sparse=False):
 def get_model(cuda, feature_sizes, pars, dynamic_quantization=False, static_quantization=False,
               quantization_aware=False, field_size=39, deep_nodes=400, h_depth=3, logger=None):
     """utils/util.py:56-73."""
-    return DeepFMs(field_size=field_size, feature_sizes=feature_sizes, embedding_size=pars.embedding_size,
-                   n_epochs=pars.n_epochs, verbose=False, use_cuda=cuda, use_fm=pars.use_fm, use_fwfm=pars.use_fwfm,
-                   use_ffm=pars.use_ffm, use_deep=pars.use_deep, batch_size=pars.batch_size,
-                   learning_rate=pars.learning_rate, weight_decay=pars.l2, momentum=pars.momentum,
-                   sparse=pars.sparse, warm=pars.warm, h_depth=pars.h_depth, deep_nodes=pars.deep_nodes,
-                   num_deeps=pars.num_deeps, numerical=pars.numerical, use_lw=pars.use_lw, use_fwlw=pars.use_fwlw,
-                   use_logit=pars.use_logit, random_seed=pars.random_seed, quantization_aware=quantization_aware,
-                   dynamic_quantization=dynamic_quantization, static_quantization=static_quantization,
-                   loss_type=pars.loss_type, embedding_bag=pars.emb_bag, qr_flag=pars.qr_emb,
-                   qr_operation=pars.qr_operation, qr_collisions=pars.qr_collisions, qr_threshold=pars.qr_threshold,
-                   logger=logger)
+    m = DeepFMs(field_size=field_size, feature_sizes=feature_sizes, embedding_size=pars.embedding_size,
+                n_epochs=pars.n_epochs, verbose=False, use_cuda=cuda, use_fm=pars.use_fm, use_fwfm=pars.use_fwfm,
+                use_ffm=pars.use_ffm, use_deep=pars.use_deep, batch_size=pars.batch_size,
+                learning_rate=pars.learning_rate, weight_decay=pars.l2, momentum=pars.momentum,
+                sparse=pars.sparse, warm=pars.warm, h_depth=pars.h_depth, deep_nodes=pars.deep_nodes,
+                num_deeps=pars.num_deeps, numerical=pars.numerical, use_lw=pars.use_lw, use_fwlw=pars.use_fwlw,
+                use_logit=pars.use_logit, random_seed=pars.random_seed, quantization_aware=quantization_aware,
+                dynamic_quantization=dynamic_quantization, static_quantization=static_quantization,
+                loss_type=pars.loss_type, embedding_bag=pars.emb_bag, qr_flag=pars.qr_emb,
+                qr_operation=pars.qr_operation, qr_collisions=pars.qr_collisions, qr_threshold=pars.qr_threshold,
+                logger=logger)
+    m.mlp_dtype = getattr(pars, "mlp_dtype", "f32")  # a CPU model with "bf16" raises at its first forward
+    return m

@@ -13,6 +13,7 @@
 
 #include "dfwfm_internal.h"
 #include "../../include/dfwfm_serve.h"
+#include "../../include/dfwfm_bf16.h"
 
 using namespace dfwfm;
 
@@ -61,6 +62,8 @@ struct dfwfm_model {
   float* d_fwlw;   // [F*D]
   float* d_lw;     // [F]
   float* d_bias;   // [1]
+  uint16_t* d_wbf16;  // dfwfm_model_pack_bf16: bf16 copy of the hidden layers' weights in MFMA operand order
+  bool bf16_on;       // the copy matches the dense parameters set (cleared by set_dense)
   uint64_t* d_stamps;  // diagnostics (DFWFM_DIAG stamps=)
   size_t stamps_cap;   // workgroups the stamp buffer holds
   size_t stamps_ring;  // launches kept (DFWFM_DIAG ring=), each its own slice of the buffer
@@ -142,7 +145,8 @@ void free_model(dfwfm_model* m) {
   if (!m) return;
   void* ptrs[] = {m->d_fields, m->d_upack, m->d_err,     m->d_wpack, m->d_mlp_b,   m->d_fc,  m->d_fwlw,
                   m->d_lw,     m->d_bias,  m->d_stamps,  m->d_wtpack, m->d_rsk,   m->d_ws,
-                  m->d_ell,    m->d_cnt,   m->d_spstat, m->d_pairs, m->d_pkrows, m->d_pk};
+                  m->d_ell,    m->d_cnt,   m->d_spstat, m->d_pairs, m->d_pkrows, m->d_pk,
+                  m->d_wbf16};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   delete m;
@@ -442,6 +446,7 @@ static int set_dense_impl(dfwfm_model* m, const float* field_cov, const float* f
   if (e != hipSuccess) return hip_fail(e, "pack launch");
   m->dense_set = true;
   m->sp = 0;  // new weights: the sparse tower's ELL is stale until rebuilt
+  m->bf16_on = false;  // and the bf16 copy until dfwfm_model_pack_bf16
   m->flags &= ~kPairs;  // and so is the FwFM pair list
   for (int h = 0; h < m->H; ++h) m->lin_w[h] = lin_w ? lin_w[h] : nullptr;
   return DFWFM_OK;
@@ -893,6 +898,90 @@ int dfwfm_serve_forward(dfwfm_model* m, const int64_t* xi, int64_t xi_stride, co
   sa.NC0 = m->NC0;
   e = launch_serve_mlp(sa, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, "serve MLP launch");
+  return DFWFM_OK;
+}
+
+// The bf16 deep tower (include/dfwfm_bf16.h): the gather / shallow half as dfwfm_forward_gather launches it, into the
+// caller's workspace, then the hidden layers on bf16 MFMA one launch per layer (dfwfm_bf16.hip).
+int dfwfm_bf16_abi_version(void) { return DFWFM_BF16_ABI_VERSION; }
+
+int dfwfm_model_pack_bf16(dfwfm_model* m, int enable, void* stream) {
+  if (!m) return fail(DFWFM_ERR_INVALID_ARG, "null model");
+  m->bf16_on = false;
+  if (!enable) return DFWFM_OK;  // the buffer is kept for the next enable and freed with the model (hipFree syncs)
+  if (!m->cfg.use_deep) return fail(DFWFM_ERR_UNSUPPORTED, "bf16 pack: the model has no deep tower");
+  if (!m->dense_set) return fail(DFWFM_ERR_STATE, "set_dense must precede pack_bf16");
+  if (!m->d_wbf16) {
+    int rc = dev_alloc(&m->d_wbf16, bf16_pack_elems(m->H, m->NT, m->NC0));
+    if (rc != DFWFM_OK) return rc;
+  }
+  // the layers' source pointers travel as kernel arguments: nothing staged from the stack, no synchronisation
+  hipError_t e = launch_bf16_pack(m->lin_w, m->d_wbf16, m->H, m->N, m->F * m->D, m->NT, m->NC0, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "bf16 pack launch");
+  m->bf16_on = true;
+  return DFWFM_OK;
+}
+
+int dfwfm_bf16_workspace_bytes(dfwfm_model* m, int64_t batch, size_t* bytes) {
+  if (!m || !bytes) return fail(DFWFM_ERR_INVALID_ARG, "null argument");
+  if (batch < 0) return fail(DFWFM_ERR_INVALID_ARG, "negative batch");
+  if (!m->cfg.use_deep) return fail(DFWFM_ERR_UNSUPPORTED, "bf16 forward: the model has no deep tower");
+  *bytes = bf16_workspace_bytes(m->NT, m->NC0, batch);
+  return DFWFM_OK;
+}
+
+int dfwfm_bf16_forward(dfwfm_model* m, const int64_t* xi, int64_t xi_stride, const float* xv, int64_t xv_stride,
+                       int64_t batch, float* out, void* workspace, size_t ws_bytes, void* stream) {
+  if (!m) return fail(DFWFM_ERR_INVALID_ARG, "null model");
+  if (!m->cfg.use_deep) return fail(DFWFM_ERR_UNSUPPORTED, "bf16 forward: the model has no deep tower");
+  int rc = check_inputs(m, xi, xi_stride, xv, xv_stride, batch, out);
+  if (rc != DFWFM_OK) return rc;
+  if (!m->bf16_on)
+    return fail(DFWFM_ERR_STATE, "bf16 forward: the bf16 weight copy is absent or stale (dfwfm_model_pack_bf16)");
+  if (batch == 0) return DFWFM_OK;
+  if (!workspace) return fail(DFWFM_ERR_INVALID_ARG, "null workspace");
+  const size_t need = bf16_workspace_bytes(m->NT, m->NC0, batch);
+  if (ws_bytes < need)
+    return fail(DFWFM_ERR_INVALID_ARG, "workspace of %zu bytes < %zu (dfwfm_bf16_workspace_bytes)", ws_bytes, need);
+  if (reinterpret_cast<uintptr_t>(workspace) % 16) return fail(DFWFM_ERR_INVALID_ARG, "workspace not 16-byte aligned");
+  const int64_t tiles = (batch + kBM - 1) / kBM;
+  if (tiles * m->NT > 0x7fffffff) return fail(DFWFM_ERR_UNSUPPORTED, "batch too large for the bf16 forward");
+  const size_t rows16 = (size_t)tiles * kBM;
+  Bf16Args ba;
+  memset(&ba, 0, sizeof ba);
+  float* w = static_cast<float*>(workspace);
+  float* deep_emb = w;
+  w += rows16 * m->NC0 * 16;
+  float* fs = w;
+  w += rows16;
+  ba.partial = w;
+  w += rows16 * m->NT;
+  ba.act[0] = reinterpret_cast<uint16_t*>(w);
+  ba.act[1] = ba.act[0] + rows16 * m->NT * 16;
+  // the gather launch: the MLP-free forward's kernel storing the E tile and first + second (dfwfm_forward_gather)
+  FwdArgs a;
+  fill_forward_args(m, a, xi, xi_stride, xv, xv_stride, batch, nullptr);
+  a.flags &= ~kHasDeep;
+  if (m->MT <= 3) a.flags |= kP3Pieces;
+  a.part_stride = m->NC0 * 16;
+  a.part_e = deep_emb;
+  a.part_fs = fs;
+  hipError_t e = launch_forward(a, m->D, 1, 1, 8, m->lds_inf, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "bf16 gather launch");
+  ba.deep_emb = deep_emb;
+  ba.fs = fs;
+  ba.wb = m->d_wbf16;
+  ba.mlp_b = m->d_mlp_b;
+  ba.fc = m->d_fc;
+  ba.bias = m->d_bias;
+  ba.out = out;
+  ba.batch = batch;
+  ba.H = m->H;
+  ba.N = m->N;
+  ba.NT = m->NT;
+  ba.NC0 = m->NC0;
+  e = launch_bf16_mlp(ba, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "bf16 MLP launch");
   return DFWFM_OK;
 }
 

@@ -130,7 +130,8 @@ inline unsigned fwd_grid(const FwdArgs& a, int rows) {
 // Test and diagnostics options, all in ONE environment variable: DFWFM_DIAG="key=value,key=value", read where
 // they apply (product runs set none).  Keys: r32 (0 never / 1 always the 32-sample set kernel), ng (4: four-wave
 // forward / backward), ftrain (0: fwd_kernel<TRAIN> instead of the helper-wave training forward), part3 (0: the
-// generic kernel for MLP-free models), p3ng (4 / 8: MLP-free waves), stamps / ring / ft / bwd / scatter /
+// generic kernel for MLP-free models), p3ng (4 / 8: MLP-free waves), bf16tile (0 / 1 / 2 / 3: the bf16 tower's tile per
+// wave, 16 x 16 / 16 x 80 / 32 x 80 / 32 x 80 with the weights in LDS; same logits), stamps / ring / ft / bwd / scatter /
 // drop_flags (phase stamps and phase-skip bits; results invalid).  dflt when the key is absent.
 inline int diag_opt(const char* key, int dflt) {
   const char* s = getenv("DFWFM_DIAG");
@@ -402,6 +403,28 @@ struct ServeArgs {
 };
 size_t serve_workspace_floats(int NT, int NC0, int64_t batch);
 hipError_t launch_serve_mlp(const ServeArgs& a, hipStream_t s);
+
+// bf16 deep tower (dfwfm_bf16.hip, include/dfwfm_bf16.h): the hidden layers on bf16 MFMA with f32 accumulation, one
+// launch per layer behind the gather launch, then a combine launch; every buffer but the model's parameters and its
+// bf16 weight pack is in the caller's workspace.
+struct Bf16Args {
+  const float* deep_emb;   // [rows16][NC0*16] f32 E rows of the gather launch (rows >= batch unwritten)
+  const float* fs;         // [rows16] first + second order
+  uint16_t* act[2];        // [rows16][NT*16] bf16 layer outputs, ping-pong
+  float* partial;          // [rows16][NT] the last layer's per-tile shares of deep[b]
+  const uint16_t* wb;      // bf16 weight pack, per layer [NT][KC][64 lanes][8] (bf16_pack_elems)
+  const float* mlp_b;      // [H][NT*16] f32
+  const float* fc;         // [NT*16] f32
+  const float* bias;       // [1]
+  float* out;              // [batch] logits
+  int64_t batch;
+  int32_t H, N, NT, NC0;
+};
+size_t bf16_pack_elems(int H, int NT, int NC0);               // bf16 elements of the whole pack
+size_t bf16_workspace_bytes(int NT, int NC0, int64_t batch);  // every region a multiple of 16 bytes
+// bf16(W_l) of every hidden layer into `wb`, from the row-major f32 weights w[l] [N][K_l] (K_0 = K0, else N)
+hipError_t launch_bf16_pack(const float* const* w, uint16_t* wb, int H, int N, int K0, int NT, int NC0, hipStream_t s);
+hipError_t launch_bf16_mlp(const Bf16Args& a, hipStream_t s);
 
 // dW_l += G_l^T X_{l-1} and db_l += sum_b G_l for every layer in one launch.
 struct DwArgs {

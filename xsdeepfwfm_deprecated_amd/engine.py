@@ -71,6 +71,9 @@ class ForwardEngine:
         # forward() takes the small-batch path (forward_small) for 0 < B <= small_rows; 0: never (DeepFMs sets it
         # from its small_batch_rows for models with a deep tower)
         self.small_rows = 0
+        # forward() takes the bf16 deep tower (forward_bf16) for every B > 0, ahead of small_rows; the caller keeps
+        # the bf16 weight copy current with sync_bf16 (DeepFMs sets it from its mlp_dtype)
+        self.bf16 = False
 
     def close(self):
         if self.handle is not None and self.handle.value:
@@ -124,11 +127,12 @@ class ForwardEngine:
         self._dense_key = key
 
     def invalidate_derived(self):
-        """Forget the pruned FwFM pair list and the sparse deep tower: dfwfm_model_set_dense turns both off in
+        """Forget the pruned FwFM pair list, the sparse deep tower and the bf16 weight copy: dfwfm_model_set_dense turns them off in
         the library (and a captured training step re-packs the weights they were built from), so the next
         sync_pairs / sync_sparse must rebuild them rather than report the cached state."""
         self._pairs_key = None
         self._sparse_key = None
+        self._bf16_key = None
 
     def sync_packed(self, tables, enable: bool = True) -> bool:
         """dfwfm_model_pack_tables: the serving copy of the categorical tables (second-order row + first-order
@@ -176,9 +180,22 @@ class ForwardEngine:
         self.__dict__.pop("_ws_cache", None)  # the workspace a batch needs changes with the path
         return self._sparse_on
 
+    def sync_bf16(self, enable: bool = True) -> bool:
+        """dfwfm_model_pack_bf16: (re)build the bf16 copy of the hidden layers' weights after a weight update
+        (stream-ordered, no host synchronisation), or drop it.  Returns whether the copy is in place."""
+        key = (self._dense_key, bool(enable))
+        if key == getattr(self, "_bf16_key", None):
+            return bool(enable)
+        _lib.check(_lib.lib().dfwfm_model_pack_bf16(self.handle, int(bool(enable)), _stream_handle(self.device)),
+                   "dfwfm_model_pack_bf16")
+        self._bf16_key = key
+        return bool(enable)
+
     # -- hot path ----------------------------------------------------------
     def forward(self, xi: torch.Tensor, xv: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
         B = xi.shape[0]
+        if self.bf16 and B > 0:
+            return self.forward_bf16(xi, xv, out)
         if 0 < B <= self.small_rows:
             return self.forward_small(xi, xv, out)
         ncat = self.cfg["field_size"] - self.cfg["numerical"]
@@ -230,6 +247,38 @@ class ForwardEngine:
             n = ctypes.c_size_t(0)
             _lib.check(_lib.lib().dfwfm_serve_workspace_bytes(self.handle, B, ctypes.byref(n)),
                        "dfwfm_serve_workspace_bytes")
+            cache[B] = int(n.value)
+        return cache[B]
+
+    def forward_bf16(self, xi: torch.Tensor, xv: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+        """dfwfm_bf16_forward (include/dfwfm_bf16.h): the forward with the hidden layers on bf16 MFMA (f32
+        accumulation; gather, first order and FwFM in exact f32), after sync_bf16(True).  Deep models only
+        (DfwfmError otherwise).  A row's bits do not depend on the batch around it."""
+        B = xi.shape[0]
+        ncat = self.cfg["field_size"] - self.cfg["numerical"]
+        num = self.cfg["numerical"]
+        _require_rows(xi, "Xi", torch.int64, self.device, ncat)
+        _require_rows(xv, "Xv", torch.float32, self.device, num)
+        if out is None:
+            out = torch.empty(B, dtype=torch.float32, device=self.device)
+        xs = xi.stride(0) if ncat > 0 else 0
+        vs = xv.stride(0) if num > 0 else 0
+        ws_bytes = self._bf16_ws_bytes(B)
+        # from torch's stream-ordered caching allocator: calls in flight on several streams never share one
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device) if ws_bytes else None
+        rc = _lib.lib().dfwfm_bf16_forward(self.handle, ctypes.c_void_p(xi.data_ptr()), xs,
+                                           ctypes.c_void_p(xv.data_ptr()), vs, B,
+                                           ctypes.c_void_p(out.data_ptr()), _ptr(ws), ws_bytes,
+                                           _stream_handle(self.device))
+        _lib.check(rc, "dfwfm_bf16_forward")
+        return out
+
+    def _bf16_ws_bytes(self, B: int) -> int:
+        cache = self.__dict__.setdefault("_bf16_ws_cache", {})  # a function of the model's shape and B alone
+        if B not in cache:
+            n = ctypes.c_size_t(0)
+            _lib.check(_lib.lib().dfwfm_bf16_workspace_bytes(self.handle, B, ctypes.byref(n)),
+                       "dfwfm_bf16_workspace_bytes")
             cache[B] = int(n.value)
         return cache[B]
 
