@@ -108,6 +108,11 @@ class DeepFMs(nn.Module):
         # first-order weight in one aligned row, dfwfm_model_pack_tables), rebuilt after weight updates; the values
         # are copied, so the logits are the same bits either way
         self.pack_tables = True
+        # the fused inference forward folds the numerical fields into layer 1 of the deep tower (their embedding is
+        # Xv * v_f[0], so layer 1 takes Xv * P with P = W1 v_f[0] precomputed after each weight update: 18 K chunks
+        # instead of 25 at Criteo-39; include/dfwfm_fold.h).  A re-association of f32 sums:
+        # the logits agree with the unfolded forward's to 1e-5, not bit for bit.  False keeps layer 1 unfolded
+        self.fold_numerical = True
         # a no-grad forward of at most this many rows on a HIP device takes the small-batch serving path
         # (ForwardEngine.forward_small, include/dfwfm_serve.h: every hidden layer spread over the chip) when the model
         # has a deep tower; 0 (default): never.  Its logits agree with the default path's to rounding, not bit for bit
@@ -274,6 +279,9 @@ class DeepFMs(nn.Module):
                 d = self._field_desc(None if second is None else second[f], None if first is None else first[f])
                 tabs.append((d["emb2"], d["emb1"]))
             eng.sync_packed(tabs, self.pack_tables)
+            if self.use_deep:  # the folded layer 1, rebuilt when W1 or a numerical table changed
+                eng.sync_fold([second[f].weight.detach() for f in range(self.num)],
+                              bool(getattr(self, "fold_numerical", True)))
             eng.small_rows = max(int(getattr(self, "small_batch_rows", 0)), 0) if self.use_deep else 0
             eng.bf16 = eng.sync_bf16(self._mlp_bf16()) if self.use_deep else False
         return eng

@@ -38,7 +38,8 @@ def _units():
         u += [(s, f"{os.path.splitext(s)[0]}_d{d}.o", [f"-DDFWFM_KD={d}"]) for d in EMB_SIZES]
     return u
 HEADERS = ["dfwfm_internal.h", "dfwfm_device.h", os.path.join("..", "..", "include", "dfwfm.h"),
-           os.path.join("..", "..", "include", "dfwfm_serve.h"), os.path.join("..", "..", "include", "dfwfm_bf16.h")]
+           os.path.join("..", "..", "include", "dfwfm_serve.h"), os.path.join("..", "..", "include", "dfwfm_bf16.h"),
+           os.path.join("..", "..", "include", "dfwfm_fold.h")]
 ARCH = os.environ.get("DFWFM_OFFLOAD_ARCH", "gfx950")
 CPU_PATH = os.path.join(PKG_DIR, "libdfwfm_cpu.so")
 CPU_SOURCES = ["dfwfm_cpu.cpp"]
@@ -169,6 +170,12 @@ BF16_SIGNATURES = {
     "dfwfm_bf16_workspace_bytes": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.POINTER(ctypes.c_size_t)]),
     "dfwfm_bf16_forward": (ctypes.c_int, [_P, _P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int64, _P, _P,
                                           ctypes.c_size_t, _P]),
+}
+
+# the folded layer 1 of the fused inference forward (include/dfwfm_fold.h): same library, its own header and ABI version
+FOLD_SIGNATURES = {
+    "dfwfm_fold_abi_version": (ctypes.c_int, []),
+    "dfwfm_model_fold_numerical": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), _P]),
 }
 
 _lib = None
@@ -376,6 +383,12 @@ def lib():
             fn.argtypes = args
         if L.dfwfm_bf16_abi_version() != 1:
             raise DfwfmError("libdfwfm bf16 ABI mismatch")
+        for name, (res, args) in FOLD_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        if L.dfwfm_fold_abi_version() != 1:
+            raise DfwfmError("libdfwfm fold ABI mismatch")
         _lib = L
     return _lib
 

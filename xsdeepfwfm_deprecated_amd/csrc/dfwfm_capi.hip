@@ -14,6 +14,7 @@
 #include "dfwfm_internal.h"
 #include "../../include/dfwfm_serve.h"
 #include "../../include/dfwfm_bf16.h"
+#include "../../include/dfwfm_fold.h"
 
 using namespace dfwfm;
 
@@ -64,6 +65,12 @@ struct dfwfm_model {
   float* d_bias;   // [1]
   uint16_t* d_wbf16;  // dfwfm_model_pack_bf16: bf16 copy of the hidden layers' weights in MFMA operand order
   bool bf16_on;       // the copy matches the dense parameters set (cleared by set_dense)
+  // dfwfm_model_fold_numerical (include/dfwfm_fold.h): layer 1's folded forward fragments [NT][foldNC][64]
+  int foldNC;          // chunks of the folded pack (0: this model never folds)
+  int foldSX, foldW0;  // the folded tile's row stride and valid columns past the E tile's start
+  int foldSh;          // floats the E tile is shifted so that its categorical block starts 16-byte aligned
+  size_t fold_lds_inf, fold_lds_r32;
+  bool fold_on;        // the pack matches the dense parameters and tables set (cleared by set_dense / set_tables)
   uint64_t* d_stamps;  // diagnostics (DFWFM_DIAG stamps=)
   size_t stamps_cap;   // workgroups the stamp buffer holds
   size_t stamps_ring;  // launches kept (DFWFM_DIAG ring=), each its own slice of the buffer
@@ -298,6 +305,32 @@ int dfwfm_model_create(const dfwfm_config* cfg, dfwfm_model** out) {
     free_model(m);
     return fail(DFWFM_ERR_UNSUPPORTED, "LDS tile of %zu bytes exceeds 160 KiB", m->lds_bytes);
   }
+  // the folded layer 1 (include/dfwfm_fold.h), decided here once for every fused inference form of the model: the
+  // pack's chunk count (the static 25-chunk forms run 18 or 25, see kFoldNS) and the activation tile -- the E tile
+  // shifted by foldSh so that its categorical block starts 16-byte aligned, Xv and the zero pad behind it
+  if (c.use_deep && m->num > 0) {
+    const int KC = (F - m->num) * D;
+    const int nc = (KC + m->num + 15) / 16;
+    const bool st = m->NC0 == 25 && NT == 25;
+    const int ncp = st ? (nc <= kFoldNS ? kFoldNS : 25) : nc;
+    const int sh = (4 - (m->num * D) % 4) % 4;
+    const int w0 = 4 * m->S * D > m->num * D + ncp * 16 ? 4 * m->S * D : m->num * D + ncp * 16;
+    int sx = r4(sh + w0 > NT * 16 ? sh + w0 : NT * 16);
+    if (!((sx >> 2) & 1)) sx += 4;  // an odd count of 16-byte units per row, as 404 is: rows spread over the LDS banks
+    const size_t l_inf = sizeof(float) * (size_t)lds_layout(F, D, m->MT, m->S, sx, m->SY, m->TPWI > 0 ? m->TPWI : 1, 1,
+                                                            true, m->tailI != 0, m->NG).total;
+    const size_t l_r32 = m->r32 ? fwd32_lds_bytes(F, D, m->MT, m->S, sx) : 0;
+    // fits, and fwd32 keeps its second workgroup per CU (80 KB each) where it has one
+    const bool fits = l_inf <= 160 * 1024 && l_r32 <= 160 * 1024 && !(m->lds_r32 <= 80 * 1024 && l_r32 > 80 * 1024);
+    if (fits && sh % 2 == 0) {
+      m->foldNC = ncp;
+      m->foldSX = sx;
+      m->foldW0 = w0;
+      m->foldSh = sh;
+      m->fold_lds_inf = l_inf;
+      m->fold_lds_r32 = l_r32;
+    }
+  }
 
   int rc = DFWFM_OK;
   if ((rc = dev_alloc(&m->d_fields, F)) || (rc = dev_alloc(&m->d_upack, (size_t)m->MT * m->S * 64)) ||
@@ -313,7 +346,7 @@ int dfwfm_model_create(const dfwfm_config* cfg, dfwfm_model** out) {
   }
   if (c.use_deep) {
     m->wpack_elems = (size_t)NT * m->NC0 * 64 + (size_t)(H - 1) * NT * NT * 64;
-    if (m->wpack_elems * sizeof(float4) >= (size_t)1 << 31) {
+    if ((m->wpack_elems + (size_t)NT * m->foldNC * 64) * sizeof(float4) >= (size_t)1 << 31) {
       free_model(m);
       return fail(DFWFM_ERR_UNSUPPORTED, "packed MLP weights exceed the 2 GiB buffer-descriptor range");
     }
@@ -321,7 +354,9 @@ int dfwfm_model_create(const dfwfm_config* cfg, dfwfm_model** out) {
     m->wtpack_elems = m->wpack_elems;
     m->wt_off[1] = 0;
     for (int l = 2; l <= H; ++l) m->wt_off[l] = m->wt_off[l - 1] + (l == 2 ? m->NC0 : NT) * NT * 64;
-    if ((rc = dev_alloc(&m->d_wtpack, m->wtpack_elems)) || (rc = dev_alloc(&m->d_wpack, m->wpack_elems)) ||
+    // (the folded layer 1's fragments live behind the unfolded layers in d_wpack: one buffer descriptor serves both)
+    if ((rc = dev_alloc(&m->d_wtpack, m->wtpack_elems)) ||
+        (rc = dev_alloc(&m->d_wpack, m->wpack_elems + (size_t)NT * m->foldNC * 64)) ||
         (rc = dev_alloc(&m->d_mlp_b, (size_t)H * NT * 16)) || (rc = dev_alloc(&m->d_fc, (size_t)NT * 16))) {
       free_model(m);
       return rc;
@@ -370,6 +405,7 @@ int dfwfm_model_set_tables(dfwfm_model* m, const dfwfm_field_tables* t, int32_t 
     if (host[f].c > 0) host[f].n = (host[f].n + host[f].c - 1) / host[f].c * host[f].c;
   memcpy(m->h_fields, host, sizeof(FieldDev) * n);
   m->pkw = 0;  // the serving copy was built from the old tables
+  m->fold_on = false;  // and so was the folded layer 1 (the numerical tables' row 0)
   m->flags &= ~kHasQR;
   for (int f = 0; f < n; ++f)
     if (host[f].c > 0) m->flags |= kHasQR;
@@ -447,6 +483,7 @@ static int set_dense_impl(dfwfm_model* m, const float* field_cov, const float* f
   m->dense_set = true;
   m->sp = 0;  // new weights: the sparse tower's ELL is stale until rebuilt
   m->bf16_on = false;  // and the bf16 copy until dfwfm_model_pack_bf16
+  m->fold_on = false;  // and the folded layer 1 until dfwfm_model_fold_numerical
   m->flags &= ~kPairs;  // and so is the FwFM pair list
   for (int h = 0; h < m->H; ++h) m->lin_w[h] = lin_w ? lin_w[h] : nullptr;
   return DFWFM_OK;
@@ -530,6 +567,17 @@ void fill_forward_args(const dfwfm_model* m, FwdArgs& a, const int64_t* xi, int6
   memcpy(a.fw_list8, m->fw_list8, sizeof a.fw_list8);
   memcpy(a.fw_off4, m->fw_off4, sizeof a.fw_off4);
   memcpy(a.fw_off8, m->fw_off8, sizeof a.fw_off8);
+}
+
+// dfwfm_forward / dfwfm_forward_batches with the fold on: layer 1 from the folded pack, the folded tile's geometry
+void apply_fold(const dfwfm_model* m, FwdArgs& a) {
+  if (!m->fold_on) return;
+  a.wfold_off = (int32_t)m->wpack_elems;
+  a.wpack_bytes = (int32_t)((m->wpack_elems + (size_t)m->NT * m->foldNC * 64) * sizeof(float4));
+  a.NC0f = m->foldNC;
+  a.xsh = m->foldSh;
+  a.SX = m->foldSX;
+  a.W0 = m->foldW0;
 }
 
 // The weight-gradient GEMM's grid for `batch` rows: 80 x 80 blocks per layer (per_split of them over all layers) in
@@ -702,9 +750,11 @@ int dfwfm_forward(dfwfm_model* m, const int64_t* xi, int64_t xi_stride, const fl
   // diagnostics only: DFWFM_DIAG stamps=1 records per-workgroup phase clocks (dfwfm_diag_stamps)
   if ((rc = diag_stamps_buffer(m, batch, 1, &a.stamps)) != DFWFM_OK) return rc;
   a.tail = m->tailI;
+  apply_fold(m, a);
   const bool r32 = (a.flags & kHasDeep) && use_fwd32(m, batch, stream);
-  hipError_t e = r32 ? launch_fwd32(a, m->D, m->lds_r32, (hipStream_t)stream)
-                     : launch_forward(a, m->D, m->TPWI > 0 ? m->TPWI : 1, m->KS, m->NG, m->lds_inf, (hipStream_t)stream);
+  hipError_t e = r32 ? launch_fwd32(a, m->D, m->fold_on ? m->fold_lds_r32 : m->lds_r32, (hipStream_t)stream)
+                     : launch_forward(a, m->D, m->TPWI > 0 ? m->TPWI : 1, m->KS, m->NG,
+                                      m->fold_on ? m->fold_lds_inf : m->lds_inf, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, "forward launch");
   return DFWFM_OK;
 }
@@ -740,6 +790,7 @@ int dfwfm_forward_batches(dfwfm_model* m, int32_t nb, const int64_t* const* xi, 
     // 30.33 -> 30.08 us per batch at 2000 steps, 31.3 -> 31.05 on a 20-batch set (r03be)
     a.flags |= kPrio | kPrioEpi | kDeferTail;
     a.tail = m->tailI;
+    apply_fold(m, a);
     if (n > 1) {
       a.nb = n;
       a.tiles = (int32_t)((batch + rows - 1) / rows);
@@ -751,9 +802,9 @@ int dfwfm_forward_batches(dfwfm_model* m, int32_t nb, const int64_t* const* xi, 
     }
     int rc = diag_stamps_buffer(m, (int64_t)n * a.tiles * rows, 1, &a.stamps);
     if (rc != DFWFM_OK) return rc;
-    const hipError_t e = r32 ? launch_fwd32(a, m->D, m->lds_r32, (hipStream_t)stream)
-                             : launch_forward(a, m->D, m->TPWI > 0 ? m->TPWI : 1, m->KS, m->NG, m->lds_inf,
-                                              (hipStream_t)stream);
+    const hipError_t e = r32 ? launch_fwd32(a, m->D, m->fold_on ? m->fold_lds_r32 : m->lds_r32, (hipStream_t)stream)
+                             : launch_forward(a, m->D, m->TPWI > 0 ? m->TPWI : 1, m->KS, m->NG,
+                                              m->fold_on ? m->fold_lds_inf : m->lds_inf, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "batch-set forward launch");
   }
   return DFWFM_OK;
@@ -982,6 +1033,43 @@ int dfwfm_bf16_forward(dfwfm_model* m, const int64_t* xi, int64_t xi_stride, con
   ba.NC0 = m->NC0;
   e = launch_bf16_mlp(ba, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, "bf16 MLP launch");
+  return DFWFM_OK;
+}
+
+// The folded layer 1 of the fused inference forward (include/dfwfm_fold.h)
+int dfwfm_fold_abi_version(void) { return DFWFM_FOLD_ABI_VERSION; }
+
+int dfwfm_model_fold_numerical(dfwfm_model* m, int32_t enable, int32_t* enabled, void* stream) {
+  if (!m || !enabled) return fail(DFWFM_ERR_INVALID_ARG, "null argument");
+  *enabled = 0;
+  if (!enable) {
+    m->fold_on = false;
+    return DFWFM_OK;
+  }
+  if (!m->tables_set || !m->dense_set)
+    return fail(DFWFM_ERR_STATE, "set_tables and set_dense must precede fold_numerical");
+  // no deep tower, no numerical field or a tile that does not fit (foldNC == 0); DFWFM_DIAG fold=0: forced off
+  if (m->foldNC == 0 || !m->lin_w[0] || diag_opt("fold", 1) == 0) {
+    m->fold_on = false;
+    return DFWFM_OK;
+  }
+  // the sources travel as kernel arguments (W1 of the last set_dense, the device field descriptors of the last
+  // set_tables): nothing staged from the stack, no synchronisation
+  FoldPackArgs fa;
+  memset(&fa, 0, sizeof fa);
+  fa.w1 = m->lin_w[0];
+  fa.fields = m->d_fields;
+  fa.dst = m->d_wpack + m->wpack_elems;
+  fa.N = m->N;
+  fa.F = m->F;
+  fa.D = m->D;
+  fa.num = m->num;
+  fa.NT = m->NT;
+  fa.NC = m->foldNC;
+  hipError_t e = launch_pack_fold(fa, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "fold pack launch");
+  m->fold_on = true;
+  *enabled = 1;
   return DFWFM_OK;
 }
 

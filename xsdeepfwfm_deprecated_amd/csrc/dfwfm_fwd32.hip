@@ -14,6 +14,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "dfwfm_device.h"
 #include "dfwfm_internal.h"
 
@@ -26,6 +28,8 @@ constexpr int kRows = 16 * kRT;  // samples per workgroup
 constexpr int kNG = 8;           // waves (output-tile groups), two per SIMD
 constexpr int kTPW = 3;          // whole output tiles per wave: 25 = 8 x 3 + the split 25th
 constexpr int kNS = 25;          // K chunks of every layer (static K loop)
+constexpr int kNSF = kFoldNS;    // K chunks of layer 1 over the folded pack (include/dfwfm_fold.h)
+static_assert(kNSF == kNS - 7, "k_loop_rt's folded form jumps over seven of the kNS steps");
 constexpr int kNTH = 64 * kNG;
 
 // the activation tile (in place), the sums that live to the end, and a scratch region used first by the shallow
@@ -68,33 +72,58 @@ __device__ __forceinline__ void mfma_chunk_rt(f32x4 (&acc)[RT][TPW], const float
       }
 }
 
+template <int B, int E, class Fn>
+__device__ __forceinline__ void static_for(Fn&& f) {
+  if constexpr (B < E) {
+    f(std::integral_constant<int, B>{});
+    static_for<B + 1, E>(f);
+  }
+}
+
 // mlp_k_loop_s for RT row tiles: the NS-chunk static K loop with three rotating weight / activation register
 // sets, refills two chunks ahead, and the wave's share of the split tile riding on the sets the last two steps
-// free (multiplied after the loop into tp[rt])
+// free (multiplied after the loop into tp[rt]).
+// skip (wave-uniform): the folded layer 1 (include/dfwfm_fold.h) -- the same unrolled steps run NS - kSkipMid - 1 =
+// kFoldNS chunks: steps [kSkipAt, kSkipAt + kSkipMid) and the last step are jumped over (a multiple of three steps in
+// the middle, so every later step keeps its register sets), and the steps behind the gap fetch chunk (step -
+// kSkipMid).  One copy of the loop serves both counts: a second instantiation beside it cost registers (spills).
+constexpr int kSkipAt = 3, kSkipMid = 6;
 template <int TPW, int RT, int NG, int NS>
 __device__ __forceinline__ void k_loop_rt(f32x4 (&acc)[RT][TPW], const float* __restrict__ act, int SA,
                                           const LayerStream<TPW, 1, NG>& ls, f32x4 (&b0)[TPW], f32x4 (&b1)[TPW],
                                           f32x4 (&b2)[TPW], int lane, const TailStream<NG>& ts, f32x4 (&tp)[RT],
-                                          bool mid_barrier) {
+                                          bool mid_barrier, bool skip) {
+  static_assert(kSkipMid % 3 == 0 && kSkipAt >= 2 && kSkipAt + kSkipMid + 2 < NS, "skipped steps keep the rotation");
   const int voff = lane * 16;
   const float* arow = act + (lane & 15) * SA + 4 * (lane >> 4);
+  const int sk = skip ? kSkipMid : 0;           // chunks the steps behind the gap are shifted by
+  const float* arow_s = arow - 16 * sk;
+  // the step that would fetch the last step's chunk: folded, that step does not run -- the last chunk again
+  const int c_pen = skip ? NS - 2 - kSkipMid : NS - 1;
   float4 a0[RT], a1[RT], a2[RT];
 #pragma unroll
   for (int rt = 0; rt < RT; ++rt) {
     a0[rt] = *reinterpret_cast<const float4*>(arow + rt * 16 * SA);
     a1[rt] = *reinterpret_cast<const float4*>(arow + rt * 16 * SA + 16);
   }
-#pragma unroll
-  for (int i = 0; i < NS; ++i) {
+  auto step = [&](auto i_) __attribute__((always_inline)) {
+    constexpr int i = decltype(i_)::value;
     f32x4 (&X)[TPW] = (i % 3 == 0) ? b0 : ((i % 3 == 1) ? b1 : b2);
     f32x4 (&Z)[TPW] = (i % 3 == 0) ? b2 : ((i % 3 == 1) ? b0 : b1);
     float4 (&AX)[RT] = (i % 3 == 0) ? a0 : ((i % 3 == 1) ? a1 : a2);
     float4 (&AZ)[RT] = (i % 3 == 0) ? a2 : ((i % 3 == 1) ? a0 : a1);
     if (i + 3 == NS && mid_barrier) __syncthreads();  // the previous layer's split tile (chunk NS - 1) is written
-    if (i + 2 < NS) {
+    if constexpr (i + 3 == NS) {  // fetches the last step's chunk
 #pragma unroll
-      for (int rt = 0; rt < RT; ++rt) AZ[rt] = *reinterpret_cast<const float4*>(arow + rt * 16 * SA + 16 * (i + 2));
-      ls.load(Z, ls.c0 + i + 2, voff);
+      for (int rt = 0; rt < RT; ++rt) AZ[rt] = *reinterpret_cast<const float4*>(arow + rt * 16 * SA + 16 * c_pen);
+      ls.load(Z, ls.c0 + c_pen, voff);
+    } else if constexpr (i + 2 < NS) {
+      // chunk i + 2 for the step two ahead; behind the gap chunk i + 2 - kSkipMid (the steps in front of the gap
+      // fetch for the first two steps behind it when it is jumped over: the same chunk numbers)
+      const float* ar = i + 2 >= kSkipAt + kSkipMid ? arow_s : arow;
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt) AZ[rt] = *reinterpret_cast<const float4*>(ar + rt * 16 * SA + 16 * (i + 2));
+      ls.load(Z, ls.c0 + i + 2 - (i + 2 >= kSkipAt + kSkipMid ? sk : 0), voff);
     } else {
       ts.template load_set<TPW>(ls.rsrc, Z, i + 2 == NS ? 0 : TPW, voff);
     }
@@ -106,7 +135,11 @@ __device__ __forceinline__ void k_loop_rt(f32x4 (&acc)[RT][TPW], const float* __
     }
     __builtin_amdgcn_sched_group_barrier(0x008, 2 * RT * TPW, 0);
     __builtin_amdgcn_sched_barrier(0);
-  }
+  };
+  static_for<0, kSkipAt>(step);
+  if (!skip) static_for<kSkipAt, kSkipAt + kSkipMid>(step);
+  static_for<kSkipAt + kSkipMid, NS - 1>(step);
+  if (!skip) step(std::integral_constant<int, NS - 1>{});  // (folded: the split tile's share is <= TPW fragments)
   // the split tile: fragments [0, TPW) in the set of step NS, [TPW, 2 TPW) in the set of step NS + 1; two
   // accumulators per row tile by chunk parity (no back-to-back dependent MFMAs), like TailStream::mma_set
   f32x4 c0[RT], c1[RT];
@@ -153,6 +186,11 @@ fwd32_kernel(FwdArgs p) {
   const int Fp = r4(F);
   const Lds32 L = lds32_layout(F, D, p.MT, p.S, SX);
   float* buf = smem + L.buf;
+  // the folded layer 1 (include/dfwfm_fold.h): the E tile shifted so that its categorical block starts 16-byte
+  // aligned, Xv[b, 0..num) and the zero pad right behind E; layer 1 reads from the categorical block's start
+  const bool fold = p.wfold_off != 0;  // wave-uniform (a kernel argument)
+  float* ebuf = buf + (fold ? p.xsh : 0);
+  const int nc1 = fold ? p.NC0f : p.NC0;
   float* fs = smem + L.fs;
   float* dsum = smem + L.dsum;
   FieldDev* desc = reinterpret_cast<FieldDev*>(smem + L.desc);
@@ -348,7 +386,7 @@ fwd32_kernel(FwdArgs p) {
       }
     }
     // layer-0 weights behind the row loads (vmcnt retires in issue order)
-    ls.init(wrsrc, 0, p.NC0, p.NT, g, 0);
+    ls.init(wrsrc, p.wfold_off, nc1, p.NT, g, 0);
     ls.preload(wb0, wb1, lane * 16);
     // the shallow parameters to LDS while the row loads are in flight
 #pragma unroll
@@ -362,11 +400,13 @@ fwd32_kernel(FwdArgs p) {
       if (i < n_fwlw) fwlw_s[i] = fw[k];
     }
     if ((flags & kFoLw) && tid < F) lw_s[tid] = lwv;
-    // zero the E-tile padding the MLP (NC0*16 columns) and the FwFM (S*4 fields) read
-    const int w = p.W0 - F * D;
+    // zero the E-tile padding the MLP (NC0*16 columns) and the FwFM (S*4 fields) read; folded: past the num Xv
+    // columns behind E (written with the numerical rows below)
+    const int zc = F * D + (fold ? num : 0);
+    const int w = p.W0 - zc;
     for (int i = tid; i < kRows * w; i += kNTH) {
       const int b = i / w;
-      buf[b * SX + F * D + (i - b * w)] = 0.f;
+      ebuf[b * SX + zc + (i - b * w)] = 0.f;
     }
 #pragma unroll
     for (int k = 0; k < RPT; ++k) {
@@ -378,7 +418,8 @@ fwd32_kernel(FwdArgs p) {
           float e[D];
 #pragma unroll
           for (int d = 0; d < D; ++d) e[d] = live[k] ? combine(mode[k], va[k][d], QR ? vb[k][d] : 0.f, scale[k]) : 0.f;
-          store_row<D>(buf + b * SX + f * D, e);
+          store_row<D>(ebuf + b * SX + f * D, e);
+          if (fold && f < num) ebuf[b * SX + F * D + f] = live[k] ? scale[k] : 0.f;
         }
         fo[b * Fp + f] = live[k] ? combine(mode[k], fa[k], QR ? fb[k] : 0.f, scale[k]) : 0.f;
       }
@@ -392,7 +433,7 @@ fwd32_kernel(FwdArgs p) {
     for (int r = tid; r < kRows * F; r += kNTH) {
       const int f = r >> 5;
       const int b = r & 31;
-      const float* e = buf + b * SX + f * D;
+      const float* e = ebuf + b * SX + f * D;
       const float* w = fwlw_s + f * D;
       float s = 0.f;
 #pragma unroll
@@ -413,7 +454,7 @@ fwd32_kernel(FwdArgs p) {
       const int nt = pc - m * D;
       const int n = nt * 16 + (lane & 15);
       const int b = n / D;
-      const float* ecol0 = buf + b * SX + (n - b * D);  // E[b][l][d] = ecol0[l * D]; the second half 16 rows on
+      const float* ecol0 = ebuf + b * SX + (n - b * D);  // E[b][l][d] = ecol0[l * D]; the second half 16 rows on
       const float* ecol1 = ecol0 + 16 * SX;
       const float* ua = upk + m * S * 64 + lane;
       f32x4 acc0 = f32x4{0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
@@ -513,13 +554,13 @@ fwd32_kernel(FwdArgs p) {
   };
   f32x4 bq[kTPW];
   load_bias(bq, 0, 4 * (lane >> 4));
-  int layer_off = 0;
+  int layer_off = p.wfold_off;  // layer 1: the folded pack behind the unfolded layers, or 0
   for (int h = 0; h < p.H; ++h) {
     int lv = lane;
     asm volatile("" : "+v"(lv));
     const int rowl = lv & 15;
     const int nq = 4 * (lv >> 4);
-    const int NC = h == 0 ? p.NC0 : p.NT;
+    const int NC = h == 0 ? nc1 : p.NT;
     const bool last = h == p.H - 1;
     const int boff = __builtin_amdgcn_readfirstlane((h * p.NT + TT) * 64 + (g & 3) * 4);
     const int ntail = TT * 16 + nq + (g & 3);
@@ -534,7 +575,10 @@ fwd32_kernel(FwdArgs p) {
     f32x4 tp[kRT];
     // kDeferTail: the barrier after the split tile's reduction waits inside this K loop, right before chunk NS - 1
     // (the split tile's columns) is read -- until then the waves that did not reduce run their MFMAs
-    k_loop_rt<kTPW, kRT, kNG, kNS>(acc, buf, SX, ls, wb0, wb1, wb2, lane, ts, tp, h > 0 && (flags & kDeferTail));
+    // the folded layer 1 reads categorical E, the num Xv columns, zeros: from E column num * D (16-byte aligned),
+    // kNSF chunks of it when that is the pack's count (else kNS over a zero-padded pack)
+    k_loop_rt<kTPW, kRT, kNG, kNS>(acc, h == 0 && fold ? ebuf + num * D : buf, SX, ls, wb0, wb1, wb2, lane, ts, tp,
+                                   h > 0 && (flags & kDeferTail), h == 0 && nc1 == kNSF);
     if (flags & kPrioEpi) __builtin_amdgcn_s_setprio(1);
     if (h == 0) stamp(p.stamps, 12, tid);
     __syncthreads();  // every wave has read the layer's input: the tile may be overwritten
@@ -570,7 +614,7 @@ fwd32_kernel(FwdArgs p) {
         if (lane < 16) dsum[g * kRows + rt * 16 + rowl] = d;
       }
     }
-    layer_off += p.NT * NC * 64;
+    layer_off = h == 0 ? p.NT * p.NC0 * 64 : layer_off + p.NT * NC * 64;  // layer 2 follows the unfolded layer 1
     if (!last) {  // the next layer's first chunks and biases, ahead of the barrier (after the epilogue)
       ls.init(wrsrc, layer_off, p.NT, p.NT, g, 0);
       ls.preload(wb0, wb1, lane * 16);

@@ -43,6 +43,7 @@ constexpr int kBwdNoGStore = 1 << 20, kBwdNoMask = 1 << 21, kBwdGeneric = 1 << 2
 constexpr int kFtDiagHwId = 1 << 23, kFtDiagNoMlp = 1 << 24;
 constexpr int kMaxH = 16;      // hidden layers
 constexpr int kMaxSet = 32;    // batches per launch of dfwfm_forward_batches (the set is a kernel argument)
+constexpr int kFoldNS = 18;    // the static forms' second layer-1 chunk count: Criteo-39 folded, ceil((26*10 + 13) / 16)
 
 // Device copy of dfwfm_field_tables (same field order and sizes); for QR fields
 // n holds the accepted index bound ceil(n/c)*c.
@@ -88,6 +89,13 @@ struct FwdArgs {
   int32_t tail;        // 1: NT == 4*TPW + 1 and tile 4*TPW is split by K over the four waves
   int32_t ns;          // 25: every layer has 25 K chunks and 25 output tiles (static K loop), else 0
   int32_t flags;
+  // the folded layer 1 of the fused inference forward (include/dfwfm_fold.h), 0 when off: the float4 offset in wpack
+  // (behind the unfolded layers: one buffer descriptor serves both) of layer 1's fragments [NT][NC0f][64] over the
+  // rows (categorical columns of W1 | P[0..num) | zeros); then SX and W0 are the folded tile's, the E tile starts xsh
+  // floats into each row and layer 1 reads from E column num * D
+  int32_t wfold_off;
+  int32_t NC0f;
+  int32_t xsh;
   uint64_t* stamps;    // diagnostics only: [grid][kStampSlots] shader-clock stamps, normally null
   // training (flags & kTrain): activations kept for the backward
   float* sv_e;              // [B][F*D] E before dropout
@@ -535,6 +543,15 @@ hipError_t launch_pack_tables(const PackTabList& L, hipStream_t s);
 // the gather + shallow part alone (-> a.part_e / a.part_fs): the sparse deep tower's first launch
 hipError_t launch_forward_gather(const FwdArgs& a, int D, size_t lds1, hipStream_t s);
 hipError_t launch_pack_list(const PackList& L, int total_blocks, hipStream_t s);
+// dfwfm_model_fold_numerical: layer 1's folded forward fragments [NT][NC][64] float4 from W1 [N][F*D] and row 0 of
+// the numerical fields' second-order tables (read through the device descriptors)
+struct FoldPackArgs {
+  const float* w1;
+  const FieldDev* fields;
+  float4* dst;
+  int32_t N, F, D, num, NT, NC;
+};
+hipError_t launch_pack_fold(const FoldPackArgs& a, hipStream_t s);
 // the fused inference forward on 32-sample workgroups (dfwfm_fwd32.hip): both 16-row tiles per wave in the MLP;
 // the static 3x400 form only (fwd32_supported), bit-identical logits to fwd_kernel's
 bool fwd32_supported(int F, int D, int H, int NT, int NC0, int tailI, int NG);

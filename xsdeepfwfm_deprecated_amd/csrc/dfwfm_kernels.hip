@@ -105,6 +105,13 @@ fwd_kernel(FwdArgs p) {
   float* part2 = smem + L.part2;
   float* dsum = smem + L.dsum;
   float* fs = smem + L.fs;
+  // the folded layer 1 (include/dfwfm_fold.h; the fused inference forward only): the E tile shifted so that its
+  // categorical block starts 16-byte aligned, Xv[b, 0..num) and the zero pad right behind E; layer 1 reads from the
+  // categorical block's start.  Wave-uniform (a kernel argument).
+  const bool fold = PART == 0 && !TRAIN && p.wfold_off != 0;
+  const int off1 = fold ? p.wfold_off : 0;  // layer 1's float4 offset in wpack: the folded pack behind the unfolded layers
+  float* bufE = bufX + (fold ? p.xsh : 0);
+  const int nc1 = fold ? p.NC0f : p.NC0;
 
   const TileRef tr = tile_ref<kBM>(p);  // batch set: this workgroup's batch
   const int64_t b0 = tr.b0;
@@ -348,7 +355,7 @@ fwd_kernel(FwdArgs p) {
     // issuing them earlier would make every gather wait for 56 KB of weights) and land during the combine,
     // the shallow part and the barriers
     if (deep) {
-      ls.init(wrsrc, 0, p.NC0, p.NT, g, kh);
+      ls.init(wrsrc, off1, nc1, p.NT, g, kh);
       DFWFM_PRELOAD(ls);
     }
     if constexpr (!QR)  // PART 3: behind the row loads (vmcnt retires in order); QR: no room
@@ -365,11 +372,13 @@ fwd_kernel(FwdArgs p) {
       if (i < n_fwlw) fwlw_s[i] = fw[k];
     }
     if ((flags & kFoLw) && tid < F) lw_s[tid] = lwv;
-    // zero the E-tile padding read by the MLP (NC0*16 columns) and the FwFM (S*4 fields)
-    const int w = p.W0 - F * D;
+    // zero the E-tile padding read by the MLP (NC0*16 columns) and the FwFM (S*4 fields); folded: past the num Xv
+    // columns behind E (written with the numerical rows below)
+    const int zc = F * D + (fold ? num : 0);
+    const int w = p.W0 - zc;
     for (int i = tid; i < kBM * w; i += NTH) {
       const int b = i / w;
-      bufX[b * SX + F * D + (i - b * w)] = 0.f;
+      bufE[b * SX + zc + (i - b * w)] = 0.f;
     }
     // ... then combine and store
 #pragma unroll
@@ -382,7 +391,8 @@ fwd_kernel(FwdArgs p) {
           float e[D];
 #pragma unroll
           for (int d = 0; d < D; ++d) e[d] = live[k] ? combine(mode[k], va[k][d], QR ? vb[k][d] : 0.f, scale[k]) : 0.f;
-          store_row<D>(bufX + b * SX + f * D, e);
+          store_row<D>(bufE + b * SX + f * D, e);
+          if (fold && f < num) bufE[b * SX + F * D + f] = live[k] ? scale[k] : 0.f;
         }
         fo[b * Fp + f] = live[k] ? combine(mode[k], fa[k], QR ? fb[k] : 0.f, scale[k]) : 0.f;
       }
@@ -408,7 +418,7 @@ fwd_kernel(FwdArgs p) {
     for (int r = tid; r < kBM * F; r += NTH) {
       const int f = r >> 4;
       const int b = r & 15;
-      const float* e = bufX + b * SX + f * D;
+      const float* e = bufE + b * SX + f * D;
       const float* w = fwlw_s + f * D;
       float s = 0.f;
 #pragma unroll
@@ -554,7 +564,7 @@ fwd_kernel(FwdArgs p) {
       const int nt = pc - m * D;
       const int n = nt * 16 + (lane & 15);
       const int b = n / D;
-      const float* ecol = bufX + b * SX + (n - b * D);  // E[b][l][d] = ecol[l * D]
+      const float* ecol = bufE + b * SX + (n - b * D);  // E[b][l][d] = ecol[l * D]
       const float* ua = upk + m * S * 64 + lane;        // A fragment of step s: ua[s * 64]
       f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
       // steps in groups: every operand of a group is read from LDS before its MFMAs
@@ -591,7 +601,7 @@ fwd_kernel(FwdArgs p) {
   // layer 0's tail fragments once the gather rows are dead (live across the gather, they spilled)
   if constexpr (NSK == 0) {
     if (deep && tail) {
-      ts.init(0, p.NC0, TT, g);
+      ts.init(off1, nc1, TT, g);
       ts.load(wrsrc, tw, lane * 16);
     }
   }
@@ -696,7 +706,7 @@ fwd_kernel(FwdArgs p) {
   };
   f32x4 bq[TPW];
   load_bias(bq, 0, 4 * (lane >> 4));
-  int layer_off = 0;  // float4 offset of layer h in wpack
+  int layer_off = off1;  // float4 offset of layer h in wpack
   for (int h = 0; h < p.H; ++h) {
     // the lane-derived epilogue values are recomputed per layer: hoisted out of the loop they stay live across
     // it and spill, and a reload after the next layer's preload waits for the whole preload (vmcnt order)
@@ -705,11 +715,11 @@ fwd_kernel(FwdArgs p) {
     const int rowl = lv & 15;
     const int nq = 4 * (lv >> 4);
     const bool even = (h & 1) == 0;
-    const float* in = even ? bufX : bufY;
+    const float* in = h == 0 ? bufE + (fold ? num * D : 0) : (even ? bufX : bufY);
     const int SA = even ? SX : SY;
     float* outa = even ? bufY : bufX;
     const int SO = even ? SY : SX;
-    const int NC = h == 0 ? p.NC0 : p.NT;
+    const int NC = h == 0 ? nc1 : p.NT;
     const bool last = h == p.H - 1;
     // the tail tile's bias (one neuron per lane of waves 0..3), fetched before the K loop
     const int boff = __builtin_amdgcn_readfirstlane((h * p.NT + TT) * 64 + (g & 3) * 4);
@@ -725,7 +735,14 @@ fwd_kernel(FwdArgs p) {
       if (tail) ts.init(layer_off, NC, TT, g);
       else ts.cnt = 0;
       f32x4 tp;
-      mlp_k_loop_s<TPW, NG, NSK, true>(acc, in, SA, ls, wb0, wb1, wb2, lane, ts, tp);
+      bool folded1 = false;
+      if constexpr (PART == 0 && !TRAIN && NSK == 25) {
+        if (h == 0 && nc1 == kFoldNS) {  // the folded layer 1 of Criteo-39: its own static count
+          folded1 = true;
+          mlp_k_loop_s<TPW, NG, kFoldNS, true>(acc, in, SA, ls, wb0, wb1, wb2, lane, ts, tp);
+        }
+      }
+      if (!folded1) mlp_k_loop_s<TPW, NG, NSK, true>(acc, in, SA, ls, wb0, wb1, wb2, lane, ts, tp);
       if (tail) reinterpret_cast<f32x4*>(tailr)[g * 64 + lane] = tp;
     } else {
       // the tail tile's share first: its fragments (loaded with the preload) are then dead during the K loop
@@ -789,7 +806,7 @@ fwd_kernel(FwdArgs p) {
     }
     // next layer's first chunks and biases go out now, ahead of the barrier -- but after the epilogue: once
     // they are issued, any wait on a vector-memory result (a spill reload) waits for them too
-    layer_off += p.NT * NC * 64;
+    layer_off = h == 0 ? p.NT * p.NC0 * 64 : layer_off + p.NT * NC * 64;  // layer 2 follows the unfolded layer 1
     if (!last) {
       ls.init(wrsrc, layer_off, p.NT, p.NT, g, kh);
       DFWFM_PRELOAD(ls);
@@ -1102,6 +1119,47 @@ hipError_t launch_pack_tables(const PackTabList& L, hipStream_t s) {
 hipError_t launch_pack_list(const PackList& L, int total_blocks, hipStream_t s) {
   if (total_blocks <= 0 || L.n <= 0) return hipSuccess;
   hipLaunchKernelGGL(pack_dense_kernel, dim3(total_blocks), dim3(256), 0, s, L);
+  return hipGetLastError();
+}
+
+// dfwfm_model_fold_numerical: layer 1's forward fragments in kPackLinear's order over the folded K rows
+//   k < (F - num) D          W1[n][num D + k]                              (the categorical columns, field order)
+//   k < (F - num) D + num    P[f][n] = sum_d W1[n][f D + d] v_f[0][d],  f = k - (F - num) D: the products are exact
+//                            in f64, summed in f64 over d = 0..D-1 in that order and rounded to f32 once
+//   else                     0
+__global__ void __launch_bounds__(256) pack_fold_kernel(const FoldPackArgs a) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)a.NT * a.NC * 64) return;
+  const int lane = (int)(i & 63);
+  const int64_t tc = i >> 6;
+  const int c = (int)(tc % a.NC);
+  const int t = (int)(tc / a.NC);
+  const int n = t * 16 + (lane & 15);
+  const int K = a.F * a.D;
+  const int KC = (a.F - a.num) * a.D;
+  float v[4];
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    const int k = 16 * c + 4 * (lane >> 4) + s;
+    v[s] = 0.f;
+    if (n < a.N && k < KC) {
+      v[s] = a.w1[(int64_t)n * K + a.num * a.D + k];
+    } else if (n < a.N && k < KC + a.num) {
+      const int f = k - KC;
+      const float* w = a.w1 + (int64_t)n * K + f * a.D;
+      const float* e = a.fields[f].emb2;
+      double acc = 0.0;
+      for (int d = 0; d < a.D; ++d) acc += (double)w[d] * (double)e[d];
+      v[s] = (float)acc;
+    }
+  }
+  a.dst[i] = make_float4(v[0], v[1], v[2], v[3]);
+}
+
+hipError_t launch_pack_fold(const FoldPackArgs& a, hipStream_t s) {
+  const int64_t total = (int64_t)a.NT * a.NC * 64;
+  if (total <= 0) return hipSuccess;
+  hipLaunchKernelGGL(pack_fold_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 #endif  // DFWFM_KD

@@ -104,6 +104,7 @@ class ForwardEngine:
         _lib.check(_lib.lib().dfwfm_model_set_tables(self.handle, arr, len(fields),
                                                      _stream_handle(self.device)), "dfwfm_model_set_tables")
         self._packed_key = None  # set_tables drops the serving copy
+        self._fold_key = None  # ... and turns the folded layer 1 off
         self._keep = arr
         self._tables_key = key
 
@@ -133,6 +134,21 @@ class ForwardEngine:
         self._pairs_key = None
         self._sparse_key = None
         self._bf16_key = None
+        self._fold_key = None  # the folded layer 1: built from W1 and the numerical tables' row 0
+
+    def sync_fold(self, tables, enable: bool = True) -> bool:
+        """dfwfm_model_fold_numerical (include/dfwfm_fold.h): (re)build the folded layer 1 of the fused inference
+        forward after a weight update (stream-ordered, no host synchronisation), or turn it off.  tables: the
+        numerical fields' second-order tables (row 0 is folded into layer 1).  Returns whether the fold is on."""
+        key = (self._dense_key, tuple((t.data_ptr(), t._version) for t in tables), bool(enable))
+        if key == getattr(self, "_fold_key", None):
+            return self._fold_on
+        en = ctypes.c_int32(0)
+        _lib.check(_lib.lib().dfwfm_model_fold_numerical(self.handle, int(bool(enable)), ctypes.byref(en),
+                                                         _stream_handle(self.device)), "dfwfm_model_fold_numerical")
+        self._fold_on = bool(en.value)
+        self._fold_key = key
+        return self._fold_on
 
     def sync_packed(self, tables, enable: bool = True) -> bool:
         """dfwfm_model_pack_tables: the serving copy of the categorical tables (second-order row + first-order

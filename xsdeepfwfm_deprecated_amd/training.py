@@ -801,10 +801,12 @@ class DevicePruner:
                    "dfwfm_prune_threshold")
         return thr
 
-    def apply(self, t, thr, sym_f=0):
+    def apply(self, t, thr, sym_f=0, owner=None):
+        """Mask t in place; owner: the parameter t aliases (`param.data` has a version counter of its own, and the
+        engine's derived state -- packed weights, serving copy, folded layer 1 -- is keyed by the parameter's)."""
         _lib.check(self.L.dfwfm_prune_apply(ctypes.c_void_p(t.data_ptr()), t.numel(), int(sym_f),
                                             ctypes.c_void_p(thr.data_ptr()), self._stream()), "dfwfm_prune_apply")
-        torch.autograd.graph.increment_version(t)
+        torch.autograd.graph.increment_version(t if owner is None else owner)
 
 
 def prune_step(model, adaptive_sparse, prune_fm, prune_r, prune_deep, emb_r, emb_corr):
@@ -822,16 +824,16 @@ def prune_step(model, adaptive_sparse, prune_fm, prune_r, prune_deep, emb_r, emb
     with torch.no_grad():
         named = list(model.named_parameters())
         if prune_fm != 0:
-            embs = [p.data for n, p in named if "fm_2nd_embeddings" in n]
-            thr = pr.threshold([(e, 0) for e in embs], adaptive_sparse * emb_r)
+            embs = [p for n, p in named if "fm_2nd_embeddings" in n]
+            thr = pr.threshold([(e.data, 0) for e in embs], adaptive_sparse * emb_r)
             for e in embs:
-                pr.apply(e, thr)
+                pr.apply(e.data, thr, owner=e)
         for name, param in named:
             if "linear" in name and "weight" in name and prune_deep != 0:
-                pr.apply(param.data, pr.threshold([(param.data, 0)], adaptive_sparse))
+                pr.apply(param.data, pr.threshold([(param.data, 0)], adaptive_sparse), owner=param)
             if name == "field_cov.weight" and prune_r != 0:
                 F_ = param.shape[0]
-                pr.apply(param.data, pr.threshold([(param.data, F_)], adaptive_sparse * emb_corr), F_)
+                pr.apply(param.data, pr.threshold([(param.data, F_)], adaptive_sparse * emb_corr), F_, owner=param)
 
 
 def _prune_step_host(model, adaptive_sparse, prune_fm, prune_r, prune_deep, emb_r, emb_corr):
