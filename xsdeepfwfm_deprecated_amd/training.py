@@ -634,7 +634,7 @@ class FusedTrainStep:
     def _direct_inputs(self, xi, xv, y, n):
         """(xi, xv, y) as the graphs can read them in place, or None (then they are copied): a full batch of
         row-contiguous int64 indices, float32 values and float32 labels on this device."""
-        xi2 = xi.reshape(n, -1) if xi.is_contiguous() else None
+        xi2 = xi.reshape(n, -1) if (xi.is_contiguous() and self.ncat) else None  # ncat == 0: the step's own buffer
         if (xi2 is None or xi2.dtype != torch.int64 or xi2.device != self.dev or xi2.shape[1] != self.xi.shape[1]
                 or y.dtype != torch.float32 or y.device != self.dev or y.dim() != 1 or not y.is_contiguous()
                 or y.shape[0] != n):
@@ -659,7 +659,8 @@ class FusedTrainStep:
         direct = self._direct_inputs(xi, xv, y, n) if (use_graph and self.resident_inputs) else None
         if direct is None:
             if n:
-                self.xi[:n].copy_(xi.reshape(n, -1))
+                if self.ncat:  # (no categorical field: xi is [n, 0], which reshape(n, -1) cannot size)
+                    self.xi[:n].copy_(xi.reshape(n, -1))
                 if self.num:
                     self.xv[:n].copy_(xv[:, :self.num])
                 self.y[:n].copy_(y)
