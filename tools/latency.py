@@ -7,7 +7,7 @@ with HIP events around it (device time) and by the host clock around launch + sy
 batch's forward is also replayed from a one-forward hipGraph (launch overhead of a serving loop that captures).
 Prints one JSON line.
 
-  python tools/latency.py [--calls 1000] [--batches 1,16,64,256,1024,4096,8192] [--small] [--bf16]
+  python tools/latency.py [--calls 1000] [--batches 1,16,64,256,1024,4096,8192] [--small] [--bf16] [--bf16-fused]
 
 --small: the small-batch serving forward (eng.forward_small, include/dfwfm_serve.h) measured beside eng.forward at
 every batch, same figures, under models["deepfwfm_small"] (the batch where it stops winning is the value to give
@@ -18,6 +18,11 @@ same figures, under models["deepfwfm_bf16"], plus bf16_mfma_frac_back_to_back = 
 the back-to-back time, as a fraction of 2.5 PF/s.  A batch that is a multiple of 4096 rows and at least 8192 (up to
 81920 = 20 x 4096, the headline's workload) is also timed as one eng.forward_batches call over its 4096-row slices:
 forward_batches_4096_us (per call) and forward_batches_4096_us_per_batch in the f32 row.
+
+--bf16-fused (implies --bf16): the one-launch bf16 forward (eng.forward_bf16_fused, include/dfwfm_bf16_fused.h) beside
+eng.forward and eng.forward_bf16 in the same process, under models["deepfwfm_bf16_fused"]; and the batch-set leg also
+through eng.forward_bf16_batches: forward_bf16_batches_4096_us and forward_bf16_batches_4096_us_per_batch in that row
+(81920 rows: 20 resident batches of 4096, beside forward_batches_4096_us_per_batch of the f32 row).
 """
 import argparse
 import json
@@ -93,18 +98,19 @@ def measure(fwd, xi, xv, out, calls, dev):
             "back_to_back_us": round(e0.elapsed_time(e1) * 1e3 / (reps * 20), 2)}
 
 
-def measure_batch_set(eng, xi, xv, out, dev, reps=10):
-    """device time of one eng.forward_batches call over the 4096-row slices of (xi, xv), calls issued back to back"""
+def measure_batch_set(call, xi, xv, out, dev, reps=10):
+    """device time of one batch-set call (eng.forward_batches or eng.forward_bf16_batches) over the 4096-row slices of
+    (xi, xv), calls issued back to back"""
     nb = xi.shape[0] // 4096
     batches = [(xi[i * 4096:(i + 1) * 4096], xv[i * 4096:(i + 1) * 4096]) for i in range(nb)]
     outs = [out[i * 4096:(i + 1) * 4096] for i in range(nb)]
     st = torch.cuda.current_stream(dev)
     for _ in range(5):
-        eng.forward_batches(batches, outs)
+        call(batches, outs)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record(st)
     for _ in range(reps):
-        eng.forward_batches(batches, outs)
+        call(batches, outs)
     e1.record(st)
     e1.synchronize()
     return e0.elapsed_time(e1) * 1e3 / reps, nb
@@ -116,7 +122,10 @@ def main():
     ap.add_argument("--batches", default="1,16,64,256,1024,4096,8192")
     ap.add_argument("--small", action="store_true", help="also measure eng.forward_small (deep model)")
     ap.add_argument("--bf16", action="store_true", help="also measure eng.forward_bf16 (deep model)")
+    ap.add_argument("--bf16-fused", action="store_true",
+                    help="also measure eng.forward_bf16_fused and eng.forward_bf16_batches (deep model; implies --bf16)")
     a = ap.parse_args()
+    a.bf16 = a.bf16 or a.bf16_fused
     batches = [int(x) for x in a.batches.split(",")]
     if not batches or min(batches) < 1 or max(batches) > 81920:
         ap.error("--batches: sizes from 1 to 81920")
@@ -128,7 +137,7 @@ def main():
                    "(data/results/criteo.md:5)", "calls": a.calls, "models": {}}
     for name, deep in (("deepfwfm", 1), ("fwfm", 0)):
         m, sizes = build(deep, dev)
-        rows, small, bf16 = {}, {}, {}
+        rows, small, bf16, fused = {}, {}, {}, {}
         with torch.no_grad():
             eng = m._sync_engine(dev)
             if a.bf16 and deep:
@@ -139,21 +148,28 @@ def main():
                 out = torch.empty(b, dtype=torch.float32, device=dev)
                 calls = a.calls if b <= 256 else (max(100, a.calls // 10) if b <= 8192 else max(40, a.calls // 25))
                 for fwd, dst in ((eng.forward, rows),) + (((eng.forward_small, small),) if a.small and deep else ()) \
-                        + (((eng.forward_bf16, bf16),) if a.bf16 and deep else ()):
+                        + (((eng.forward_bf16, bf16),) if a.bf16 and deep else ()) \
+                        + (((eng.forward_bf16_fused, fused),) if a.bf16_fused and deep else ()):
                     r = measure(fwd, xi, xv, out, calls, dev)
                     r["samples_per_s_one_call_at_a_time"] = round(b / (r["device_us_median"] * 1e-6), 1)
-                    if deep and dst is not bf16:  # f32 MFMA fraction of the back-to-back rate (967,620 FLOP per sample, 157.3 TF/s)
+                    if deep and dst is not bf16 and dst is not fused:  # f32 MFMA fraction of the back-to-back rate (967,620 FLOP per sample, 157.3 TF/s)
                         r["mfma_frac_back_to_back"] = round(967620 * b / (r["back_to_back_us"] * 1e-6) / 157.3e12, 4)
-                    if dst is bf16:  # the tower alone (952,800 FLOP per sample) against the bf16 MFMA peak
+                    if dst is bf16 or dst is fused:  # the tower alone (952,800 FLOP per sample) against the bf16 MFMA peak
                         r["bf16_mfma_frac_back_to_back"] = round(952800 * b / (r["back_to_back_us"] * 1e-6) / 2.5e15, 4)
                     dst[str(b)] = r
                 if a.bf16 and deep and b >= 8192 and b % 4096 == 0:
-                    t, nb = measure_batch_set(eng, xi, xv, out, dev)
+                    t, nb = measure_batch_set(eng.forward_batches, xi, xv, out, dev)
                     rows[str(b)]["forward_batches_4096_us"] = round(t, 2)
                     rows[str(b)]["forward_batches_4096_us_per_batch"] = round(t / nb, 2)
+                    if a.bf16_fused:
+                        t, nb = measure_batch_set(eng.forward_bf16_batches, xi, xv, out, dev)
+                        fused[str(b)]["forward_bf16_batches_4096_us"] = round(t, 2)
+                        fused[str(b)]["forward_bf16_batches_4096_us_per_batch"] = round(t / nb, 2)
         res["models"][name] = rows
         if bf16:
             res["models"][name + "_bf16"] = bf16
+        if fused:
+            res["models"][name + "_bf16_fused"] = fused
         if small:
             res["models"][name + "_small"] = small
     print(json.dumps(res))

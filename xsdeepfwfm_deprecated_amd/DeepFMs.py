@@ -123,6 +123,11 @@ class DeepFMs(nn.Module):
         # the gather, first order and FwFM staying exact f32; it takes precedence over small_batch_rows.  Training is
         # f32 either way; a model without a deep tower ignores it
         self.mlp_dtype = "f32"
+        # with mlp_dtype = "bf16": the bf16 forward as ONE launch with the E tile and the activations in LDS
+        # (ForwardEngine.forward_bf16_fused, include/dfwfm_bf16_fused.h) instead of a launch per layer, and eval_by_batch's
+        # full batches as batch sets of it -- the same logits bit for bit.  Off by default; a shape the fused kernel does
+        # not support (ForwardEngine.bf16_fused_supported) silently keeps the per-layer path
+        self.bf16_fused = False
         # the device backward's gradient sums in a fixed order (dfwfm_set_deterministic; like
         # torch.use_deterministic_algorithms): two runs of a training step give the same bits, at ~+7 us (+2.6 %) per
         # step at Criteo-39 (sorted table scatter, split-K slices); on by default, False: float atomics (arrival order)
@@ -284,6 +289,7 @@ class DeepFMs(nn.Module):
                               bool(getattr(self, "fold_numerical", True)))
             eng.small_rows = max(int(getattr(self, "small_batch_rows", 0)), 0) if self.use_deep else 0
             eng.bf16 = eng.sync_bf16(self._mlp_bf16()) if self.use_deep else False
+            eng.bf16_fused = bool(eng.bf16 and getattr(self, "bf16_fused", False) and eng.bf16_fused_supported())
         return eng
 
     def _mlp_bf16(self) -> bool:
@@ -383,7 +389,8 @@ class DeepFMs(nn.Module):
                 # at most sparse_mlp_max_density of their weights are nonzero (checked once per weight update)
                 eng.sync_sparse(self.sparse_mlp_max_density)
             elif self.use_fwfm:
-                eng.sync_pairs(self.fwfm_pair_max)
+                if eng.sync_pairs(self.fwfm_pair_max):  # a pair list: the fused bf16 kernel does not run it
+                    eng.bf16_fused = False
         params = [q for q in self.parameters() if q.requires_grad]
         out, _ = torch.ops.dfwfm.forward(torch_ops.register(self), xi, xv, params, False, 0.0, 0)
         if self.strict_index_check and not self._defer_index_check:
@@ -478,10 +485,13 @@ class DeepFMs(nn.Module):
                 eng = self._sync_inference(dev)
                 alt = (eng.bf16 or eng.sync_sparse(self.sparse_mlp_max_density)) if self.use_deep else (
                     eng.sync_pairs(self.fwfm_pair_max) if self.use_fwfm else False)
-                if not alt:
+                # ... except the bf16 tower's fused form, which has batch sets of its own (dfwfm_bf16_fused_forward_batches)
+                fused = bool(self.use_deep and eng.bf16 and eng.bf16_fused)
+                if fused or not alt:
                     nfull = x_size // bs
-                    eng.forward_batches([(Xi_d[i * bs:(i + 1) * bs], Xv_d[i * bs:(i + 1) * bs]) for i in range(nfull)],
-                                        [logits[i * bs:(i + 1) * bs] for i in range(nfull)])
+                    call = eng.forward_bf16_batches if fused else eng.forward_batches
+                    call([(Xi_d[i * bs:(i + 1) * bs], Xv_d[i * bs:(i + 1) * bs]) for i in range(nfull)],
+                         [logits[i * bs:(i + 1) * bs] for i in range(nfull)])
                     for i in range(nfull):
                         sl = slice(i * bs, (i + 1) * bs)
                         total_loss += F.binary_cross_entropy_with_logits(logits[sl], y_d[sl]).double() * bs

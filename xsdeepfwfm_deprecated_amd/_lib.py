@@ -24,7 +24,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libdfwfm.so")
 # A/B of build variants only (e.g. libdfwfm_ns4.so built with DFWFM_HIPCC_FLAGS=-DDFWFM_NSETS=4)
 LOAD_PATH = os.path.join(PKG_DIR, os.environ["DFWFM_LIB"]) if os.environ.get("DFWFM_LIB") else LIB_PATH
 SOURCES = ["dfwfm_kernels.hip", "dfwfm_fwd32.hip", "dfwfm_ftrain.hip", "dfwfm_train.hip", "dfwfm_prune.hip", "dfwfm_metrics.hip", "dfwfm_sparse.hip",
-           "dfwfm_spmlp.hip", "dfwfm_serve.hip", "dfwfm_bf16.hip", "dfwfm_capi.hip"]
+           "dfwfm_spmlp.hip", "dfwfm_serve.hip", "dfwfm_bf16.hip", "dfwfm_bf16_fused.hip", "dfwfm_capi.hip"]
 # the forward / backward kernel templates are instantiated once per embedding size, each size in its own
 # translation unit (-DDFWFM_KD=<D>) so they compile in parallel; the plain object holds everything else
 EMB_SIZES = (4, 8, 10, 16, 32)
@@ -39,7 +39,7 @@ def _units():
     return u
 HEADERS = ["dfwfm_internal.h", "dfwfm_device.h", os.path.join("..", "..", "include", "dfwfm.h"),
            os.path.join("..", "..", "include", "dfwfm_serve.h"), os.path.join("..", "..", "include", "dfwfm_bf16.h"),
-           os.path.join("..", "..", "include", "dfwfm_fold.h")]
+           os.path.join("..", "..", "include", "dfwfm_bf16_fused.h"), os.path.join("..", "..", "include", "dfwfm_fold.h")]
 ARCH = os.environ.get("DFWFM_OFFLOAD_ARCH", "gfx950")
 CPU_PATH = os.path.join(PKG_DIR, "libdfwfm_cpu.so")
 CPU_SOURCES = ["dfwfm_cpu.cpp"]
@@ -170,6 +170,16 @@ BF16_SIGNATURES = {
     "dfwfm_bf16_workspace_bytes": (ctypes.c_int, [_P, ctypes.c_int64, ctypes.POINTER(ctypes.c_size_t)]),
     "dfwfm_bf16_forward": (ctypes.c_int, [_P, _P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int64, _P, _P,
                                           ctypes.c_size_t, _P]),
+}
+
+# the bf16 deep tower in one launch, with batch sets (include/dfwfm_bf16_fused.h): same library, its own header and ABI
+# version
+BF16_FUSED_SIGNATURES = {
+    "dfwfm_bf16_fused_abi_version": (ctypes.c_int, []),
+    "dfwfm_bf16_fused_supported": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int)]),
+    "dfwfm_bf16_fused_forward": (ctypes.c_int, [_P, _P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int64, _P, _P]),
+    "dfwfm_bf16_fused_forward_batches": (ctypes.c_int, [_P, ctypes.c_int32, _P, ctypes.c_int64, _P, ctypes.c_int64,
+                                                        ctypes.c_int64, _P, _P]),
 }
 
 # the folded layer 1 of the fused inference forward (include/dfwfm_fold.h): same library, its own header and ABI version
@@ -383,6 +393,12 @@ def lib():
             fn.argtypes = args
         if L.dfwfm_bf16_abi_version() != 1:
             raise DfwfmError("libdfwfm bf16 ABI mismatch")
+        for name, (res, args) in BF16_FUSED_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        if L.dfwfm_bf16_fused_abi_version() != 1:
+            raise DfwfmError("libdfwfm bf16 fused ABI mismatch")
         for name, (res, args) in FOLD_SIGNATURES.items():
             fn = getattr(L, name)
             fn.restype = res

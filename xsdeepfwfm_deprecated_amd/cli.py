@@ -69,6 +69,9 @@ def get_parser():
     a("-mlp_dtype", default="f32", type=str, choices=["f32", "bf16"],
       help="deep tower of the inference forward: f32, or bf16 MFMA with f32 accumulation (HIP only; this "
            "engine's addition, DeepFMs.mlp_dtype)")
+    a("-bf16_fused", default=0, type=int, choices=[0, 1],
+      help="with -mlp_dtype bf16: the bf16 forward as one launch, and batch sets of it in the evaluation "
+           "(DeepFMs.bf16_fused; the same logits; an unsupported shape keeps the per-layer path)")
     return p
 
 
@@ -117,4 +120,5 @@ def get_model(cuda, feature_sizes, pars, dynamic_quantization=False, static_quan
                 qr_operation=pars.qr_operation, qr_collisions=pars.qr_collisions, qr_threshold=pars.qr_threshold,
                 logger=logger)
     m.mlp_dtype = getattr(pars, "mlp_dtype", "f32")  # a CPU model with "bf16" raises at its first forward
+    m.bf16_fused = bool(getattr(pars, "bf16_fused", 0))
     return m

@@ -1,0 +1,521 @@
+// dfwfm_bf16_fused.hip -- the forward with a bf16 deep tower in ONE launch (include/dfwfm_bf16_fused.h).
+//
+// The per-layer path (dfwfm_bf16.hip) is the gather launch, a launch per hidden layer and a combine launch, with the
+// f32 E rows, every bf16 activation and the last layer's shares in the caller's workspace.  Here one workgroup of
+// eight waves owns ROWS = 16 RT rows of one batch (RT = 1, 2, 4) and carries them from Xi / Xv to the logits:
+//
+//   stage 1  descriptors, keys, the gather of the f32 E tile into LDS, the table / fwlw first order and the FwFM /
+//            FM second order as U'E pieces -- the arithmetic of the gather launch (fwd_kernel PART 3 with
+//            kP3Pieces), per 16-row sub-tile, so first + second are the bits dfwfm_forward_gather writes;
+//   stage 2  the hidden layers on v_mfma_f32_16x16x32_bf16: the weights are the A operand, 16-byte fragments of the
+//            pack of dfwfm_model_pack_bf16 streamed from L2 (wave w owns output tiles w, w + 8, ... for every row
+//            sub-tile, so a fragment feeds RT MFMAs), the activations the B operand, read from the LDS tile: layer 1
+//            from the f32 E tile, rounded with v_cvt_pk_bf16_f32 on the way, later layers from the bf16 tile the
+//            layer before wrote IN PLACE of it (a barrier between a layer's K loop and its epilogue: every wave
+//            holds all its accumulators in registers before any writes);
+//   stage 3  the last layer's share of deep per 16-neuron tile, as layer_epilogue forms it, into LDS [row][NT];
+//   stage 4  the shares added in tile order, logit = (first_second + deep) + bias, as bf16_combine_kernel.
+//
+// Every sum has the order the contract of include/dfwfm_bf16.h fixes (one accumulator per output element, K steps
+// c = 0 .. KC - 1 in turn), so the logits are the per-layer path's bit for bit, whatever RT.
+//
+// LDS (floats): [tile: ROWS x SE f32, then ROWS x SB bf16 in place][fs: ROWS][scratch: descriptors, lw, fwlw, first
+// order, FwFM column sums -- dead after stage 1, then the last layer's shares [ROWS][NT]].  SE = 4 mod 8 floats and
+// SB = 8 mod 16 bf16: the 16 rows a quarter wave reads 16 bytes of start 16 bytes apart modulo 256, no bank conflict.
+// Rows past the batch hold zeros and run through every stage (every wave reaches every barrier); nothing of them is
+// written out.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "dfwfm_device.h"
+#include "dfwfm_internal.h"
+
+namespace dfwfm {
+
+namespace {
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+
+constexpr int kFW = 8;            // waves of a workgroup
+constexpr int kFTH = 64 * kFW;
+constexpr int kFTPW = 4;          // output tiles per wave: deep_nodes <= 8 * 4 * 16 = 512
+constexpr int kFMaxF = 48;        // fields: three FwFM row tiles, as the pieces form of the gather launch
+constexpr int kFMT = 3;
+constexpr int kFPD = 3;           // fragment sets in flight in the K loop
+constexpr size_t kFLdsMax = 160 * 1024;
+
+// two f32 to two bf16, round to nearest even, NaN kept: lo in bits 0-15
+__device__ __forceinline__ uint32_t cvt_pk_bf16(float lo, float hi) {
+  uint32_t r;
+  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
+  return r;
+}
+
+struct FusedLds {
+  int tile, fs, desc, lw, fwlw, fo, part2, part, total;
+};
+
+__host__ __device__ inline FusedLds fused_layout(int rows, int F, int D, int NT, int SE, int SB) {
+  FusedLds L;
+  int o = 0;
+  const int tf = rows * SE, tb = rows * SB / 2;
+  L.tile = o;  o += r4(tf > tb ? tf : tb);
+  L.fs = o;    o += rows;
+  int s = o;
+  L.desc = s;  s += r4(14 * F);
+  L.lw = s;    s += r4(F);
+  L.fwlw = s;  s += r4(F * D);
+  L.fo = s;    s += rows * r4(F);
+  L.part2 = s; s += rows * D;  // per 16-row sub-tile, its 16 D column sums
+  int t = o;
+  L.part = t;  t += rows * NT;
+  L.total = r4(s > t ? s : t);
+  return L;
+}
+
+// the B fragment of K step c of one 16-row sub-tile, as the bf16x8 the MFMA takes: from the f32 E tile (two 16-byte
+// reads, rounded: ActFrag<true> of the per-layer path) or from the bf16 tile (one 16-byte read)
+template <bool F32IN>
+__device__ __forceinline__ u32x4 act_frag(const char* p) {
+  if constexpr (F32IN) {
+    const f32x4 lo = reinterpret_cast<const f32x4*>(p)[0];
+    const f32x4 hi = reinterpret_cast<const f32x4*>(p)[1];
+    return u32x4{cvt_pk_bf16(lo[0], lo[1]), cvt_pk_bf16(lo[2], lo[3]), cvt_pk_bf16(hi[0], hi[1]),
+                 cvt_pk_bf16(hi[2], hi[3])};
+  } else {
+    return *reinterpret_cast<const u32x4*>(p);
+  }
+}
+
+// one layer's K loop of one wave: its kFTPW output tiles (wt[j]: the tile's fragments of K step 0) times the RT row
+// sub-tiles (brow: this lane's 16 bytes of K step 0 in sub-tile 0; rt_bytes / c_bytes to the next sub-tile / K step).
+// kFPD weight fragment sets in a ring, each loaded kFPD - 1 steps ahead of its MFMAs (the L2 round trip); unrolled by
+// kFPD so no set is copied.  The activation fragments come from LDS in their own step: the other waves of the SIMD
+// cover that latency, and a ring of them cost the 32-row form its second workgroup per CU (registers).
+template <int RT, bool F32IN>
+__device__ __forceinline__ void fused_k_loop(f32x4 (&acc)[RT][kFTPW], const u32x4* const (&wt)[kFTPW], int lane,
+                                             const char* brow, int rt_bytes, int KC) {
+  constexpr int PD = RT == 1 ? kFPD : kFPD - 1;  // 32 and 64 rows: twice / four times the accumulators, one set fewer
+  constexpr int c_bytes = F32IN ? 128 : 64;
+  u32x4 wf[PD][kFTPW];
+  auto load = [&](int c, u32x4(&wq)[kFTPW]) {
+#pragma unroll
+    for (int j = 0; j < kFTPW; ++j) wq[j] = (wt[j] + c * 64)[lane];  // a wave-uniform base, the lane as the offset
+  };
+  auto mma = [&](int c, const u32x4(&wq)[kFTPW]) {
+    u32x4 aq[RT];
+#pragma unroll
+    for (int i = 0; i < RT; ++i) aq[i] = act_frag<F32IN>(brow + i * rt_bytes + c * c_bytes);
+#pragma unroll
+    for (int i = 0; i < RT; ++i) {
+      const bf16x8 x = __builtin_bit_cast(bf16x8, aq[i]);
+#pragma unroll
+      for (int j = 0; j < kFTPW; ++j)
+        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wq[j]), x, acc[i][j], 0, 0, 0);
+    }
+  };
+#pragma unroll
+  for (int p = 0; p < PD - 1; ++p)
+    if (p < KC) load(p, wf[p]);
+  int c = 0;
+  for (; c + 2 * PD - 1 <= KC; c += PD) {  // steady state: every step's refill is in range
+#pragma unroll
+    for (int p = 0; p < PD; ++p) {
+      load(c + p + PD - 1, wf[(p + PD - 1) % PD]);
+      mma(c + p, wf[p]);
+    }
+  }
+  for (; c < KC; c += PD) {  // the last 1 .. 2 PD - 2 steps (conditions wave-uniform)
+#pragma unroll
+    for (int p = 0; p < PD; ++p) {
+      if (c + p < KC) {
+        if (c + p + PD - 1 < KC) load(c + p + PD - 1, wf[(p + PD - 1) % PD]);
+        mma(c + p, wf[p]);
+      }
+    }
+  }
+}
+
+// RT: 16-row sub-tiles per workgroup; QR: some field may be a QR embedding (false: the gather carries no second
+// operand)
+template <int RT, bool QR>
+__global__ void __launch_bounds__(kFTH) __attribute__((amdgpu_waves_per_eu(RT == 4 ? 2 : 4)))
+bf16_fused_kernel(const FwdArgs p, const Bf16FusedGeo q) {
+  constexpr int D = 10;
+  constexpr int ROWS = 16 * RT;
+  constexpr int LR = RT == 1 ? 4 : (RT == 2 ? 5 : 6);  // log2(ROWS)
+  constexpr int RPT = RT == 1 ? 2 : 3;                  // gather rows per thread and pass
+  constexpr int NPASS = (ROWS * kFMaxF + kFTH * RPT - 1) / (kFTH * RPT);
+  static_assert(RT == 1 || RT == 2 || RT == 4, "16, 32 or 64 rows");
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int F = p.F;
+  const int num = p.num;
+  const int flags = p.flags;
+  const int Fp = r4(F);
+  const int SE = q.SE, SB = q.SB;
+  const FusedLds L = fused_layout(ROWS, F, D, p.NT, SE, SB);
+  float* etile = smem + L.tile;
+  uint16_t* atile = reinterpret_cast<uint16_t*>(smem + L.tile);
+  float* fs = smem + L.fs;
+  FieldDev* desc = reinterpret_cast<FieldDev*>(smem + L.desc);
+  float* lw_s = smem + L.lw;
+  float* fwlw_s = smem + L.fwlw;
+  float* fo = smem + L.fo;
+  float* part2 = smem + L.part2;
+  float* part = smem + L.part;
+  const TileRef tr = tile_ref<ROWS>(p);  // batch set: this workgroup's batch
+  const int64_t b0 = tr.b0;
+
+  // ---- stage 1: descriptors and shallow parameters to LDS, the E tile's zero padding -----------------------------
+  for (int i = tid; i < 7 * F; i += kFTH)
+    reinterpret_cast<u32x2*>(desc)[i] = reinterpret_cast<const u32x2*>(p.fields)[i];
+  if (flags & kFoFwlw)
+    for (int i = tid; i < F * D; i += kFTH) fwlw_s[i] = p.fwlw[i];
+  if ((flags & kFoLw) && tid < F) lw_s[tid] = p.lw[tid];
+  {
+    // columns [F D, WE): layer 1 reads K steps of 32 up to KC0 * 32, the FwFM fields up to 4 S
+    const int zc = F * D;
+    const int w = q.WE - zc;
+    for (int i = tid; i < ROWS * w; i += kFTH) {
+      const int b = i / w;
+      etile[b * SE + zc + (i - b * w)] = 0.f;
+    }
+  }
+  __syncthreads();
+
+  // ---- the gather: E rows and the table first order, RPT rows per thread and pass ------------------------------------
+  {
+    const bool needE = (flags & kNeedE) != 0;
+    const bool fo_tab = (flags & kFoTables) != 0;
+    constexpr int RQ = QR ? RPT : 1;
+#pragma unroll 1
+    for (int pass = 0; pass < NPASS; ++pass) {
+      const float* pa[RPT];
+      const float* pb[RQ];
+      const float* qa[RPT];
+      const float* qb[RQ];
+      float scale[RPT];
+      int mode[RPT];
+      bool live[RPT], pkrow[RPT];
+      int64_t key[RPT];  // gather row r -> field f = r / ROWS, sample b = r % ROWS: index or Xv bits
+#pragma unroll
+      for (int k = 0; k < RPT; ++k) {
+        const int r = tid + (pass * RPT + k) * kFTH;
+        const int f = r >> LR;
+        const int64_t gb = b0 + (r & (ROWS - 1));
+        live[k] = f < F && gb < p.batch;
+        key[k] = 0;
+        if (live[k]) {
+          if (f < num)
+            key[k] = __float_as_int(tr.xv[gb * p.xv_stride + f]);
+          else
+            key[k] = tr.xi[gb * p.xi_stride + (f - num)];
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < RPT; ++k) {
+        const int r = tid + (pass * RPT + k) * kFTH;
+        const int f = r >> LR;
+        pa[k] = qa[k] = nullptr;
+        if constexpr (QR) pb[k] = qb[k] = nullptr;
+        scale[k] = 1.f;
+        mode[k] = 0;
+        pkrow[k] = false;
+        if (!live[k]) continue;
+        const FieldDev fd = desc[f];
+        if (f < num) {
+          scale[k] = __int_as_float((int)key[k]);
+          pa[k] = fd.emb2;
+          qa[k] = fd.emb1;
+        } else {
+          int64_t idx = key[k];
+          if (idx < 0 || idx >= fd.n) {
+            atomicOr(p.err, DFWFM_FLAG_INDEX_OUT_OF_RANGE);
+            idx = 0;
+          }
+          if (!QR && p.pkw != 0) {  // the serving copy: second and first order in one aligned row
+            pkrow[k] = true;
+            pa[k] = p.pk[f] + idx * p.pkw;
+          } else if (!QR || fd.c == 0) {
+            pa[k] = fd.emb2 + idx * D;
+            if (fo_tab) qa[k] = fd.emb1 + idx;
+          } else if constexpr (QR) {
+            const int64_t qq = idx / fd.c;
+            const int64_t rr = idx - qq * fd.c;
+            mode[k] = fd.op == 0 ? 1 : 2;
+            pa[k] = fd.emb2 + qq * D;
+            pb[k] = fd.emb2_r + rr * D;
+            if (fo_tab) {
+              qa[k] = fd.emb1 + qq;
+              qb[k] = fd.emb1_r + rr;
+            }
+          }
+        }
+      }
+      float va[RPT][D], vb[RQ][D], fa[RPT], fb[RQ];
+#pragma unroll
+      for (int k = 0; k < RPT; ++k) {
+        fa[k] = 0.f;
+#pragma unroll
+        for (int d = 0; d < D; ++d) va[k][d] = 0.f;
+        if constexpr (QR) {
+          fb[k] = 0.f;
+#pragma unroll
+          for (int d = 0; d < D; ++d) vb[k][d] = 0.f;
+        }
+        if (live[k] && pkrow[k]) {
+          load_row_fo<D>(va[k], fa[k], pa[k]);
+        } else {
+          if (live[k] && needE) {
+            load_row<D>(va[k], pa[k]);
+            if constexpr (QR)
+              if (mode[k] != 0) load_row<D>(vb[k], pb[k]);
+          }
+          if (live[k] && fo_tab) {
+            fa[k] = *qa[k];
+            if constexpr (QR)
+              if (mode[k] != 0) fb[k] = *qb[k];
+          }
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < RPT; ++k) {
+        const int r = tid + (pass * RPT + k) * kFTH;
+        const int f = r >> LR;
+        const int b = r & (ROWS - 1);
+        if (f < F) {
+          if (needE) {
+            float e[D];
+#pragma unroll
+            for (int d = 0; d < D; ++d)
+              e[d] = live[k] ? combine(mode[k], va[k][d], QR ? vb[QR ? k : 0][d] : 0.f, scale[k]) : 0.f;
+            store_row<D>(etile + b * SE + f * D, e);
+          }
+          fo[b * Fp + f] = live[k] ? combine(mode[k], fa[k], QR ? fb[QR ? k : 0] : 0.f, scale[k]) : 0.f;
+        }
+      }
+    }
+  }
+  __syncthreads();
+
+  // ---- the shallow half: the expressions of fwd_kernel PART 3 (pieces form), per 16-row sub-tile ---------------------
+  if (flags & kFoFwlw) {
+    for (int r = tid; r < ROWS * F; r += kFTH) {
+      const int f = r >> LR;
+      const int b = r & (ROWS - 1);
+      const float* e = etile + b * SE + f * D;
+      const float* w = fwlw_s + f * D;
+      float s = 0.f;
+#pragma unroll
+      for (int d = 0; d < D; ++d) s += e[d] * w[d];
+      fo[b * Fp + f] = s;
+    }
+  }
+  if (flags & kHasSecond) {
+    // Y = U' E (rows k: fields, MT tiles of 16; columns n = b D + d of a sub-tile's 16 samples: D tiles of 16;
+    // contraction over l: S steps of 4, from step 4 m on), second[b] = sum_{k, d} E[b, k, d] Y[k, b D + d]
+    constexpr int SMAX = 4 * kFMT;
+    const int MT = p.MT, S = p.S;
+    float uf[kFMT][SMAX];
+    {
+      const float* up = p.upack;
+#pragma unroll
+      for (int m = 0; m < kFMT; ++m)
+#pragma unroll
+        for (int s = 0; s < SMAX; ++s) uf[m][s] = (m < MT && s >= 4 * m && s < S) ? up[(m * S + s) * 64 + lane] : 0.f;
+    }
+    for (int it = wave; it < RT * D; it += kFW) {
+      const int rt = it / D;
+      const int nt = it - rt * D;
+      const int n = nt * 16 + (lane & 15);
+      const int b = n / D;
+      const int d = n - b * D;
+      const float* ecol = etile + (rt * 16 + b) * SE + d;  // E[b][l][d] = ecol[l * D]
+      f32x4 acc[kFMT];
+#pragma unroll
+      for (int m = 0; m < kFMT; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int s0 = 0; s0 < SMAX; s0 += 4) {
+        float bv[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int s = s0 + u;
+          bv[u] = s < S ? ecol[(4 * s + (lane >> 4)) * D] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+          for (int m = 0; m < kFMT; ++m)
+            if (4 * m <= s0 + u && s0 + u < S && m < MT)
+              acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(uf[m][s0 + u], bv[u], acc[m], 0, 0, 0);
+      }
+      float colv = 0.f;
+#pragma unroll
+      for (int m = 0; m < kFMT; ++m) {
+        if (m < MT) {  // wave-uniform: the gather launch's kernel has exactly MT row tiles
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int k = 16 * m + 4 * (lane >> 4) + r;
+            colv = fmaf(k < F ? ecol[(k < F ? k : 0) * D] : 0.f, acc[m][r], colv);
+          }
+        }
+      }
+      colv += __shfl_xor(colv, 16);
+      colv += __shfl_xor(colv, 32);
+      if (lane < 16) part2[rt * 16 * D + n] = colv;  // column n's sum over k (row tiles in order)
+    }
+  }
+  __syncthreads();
+  // first[b] (lw projection or plain sum over fields) and second[b] (sum over d): 16 lanes per sample each take
+  // every 16th term, then a 16-lane DPP sum
+  for (int g4 = wave; g4 * 4 < ROWS; g4 += kFW) {
+    const int b = g4 * 4 + (lane >> 4);
+    const int qd = lane & 15;
+    float first = 0.f, second = 0.f;
+    for (int f0 = 0; f0 < F; f0 += 64) {
+      float x[4], l[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int f = min(f0 + 16 * k + qd, F - 1);
+        x[k] = fo[b * Fp + f];
+        l[k] = (flags & kFoLw) ? lw_s[f] : 1.f;
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) first = f0 + 16 * k + qd < F ? fmaf(x[k], l[k], first) : first;
+    }
+    if (flags & kHasSecond)
+      for (int d = qd; d < D; d += 16) second += part2[b * D + d];  // the sample's column sums
+    first = sum16(first);
+    second = sum16(second);
+    if (qd == 0) fs[b] = first + second;
+  }
+
+  // ---- stages 2 and 3: the hidden layers; the tile is read by every wave's K loop, then overwritten in place ----------
+  const int rl = lane & 15, kq = lane >> 4;
+  const int NT = p.NT;
+  const u32x4* wl = reinterpret_cast<const u32x4*>(q.wb);
+  for (int h = 0; h < p.H; ++h) {
+    const bool last = h == p.H - 1;
+    const int KC = h == 0 ? q.KC0 : q.KCN;
+    const u32x4* wt[kFTPW];
+#pragma unroll
+    for (int j = 0; j < kFTPW; ++j) {
+      int t = wave + kFW * j;
+      t = t < NT ? t : NT - 1;  // clamped duplicates, results discarded
+      wt[j] = wl + (size_t)t * KC * 64;
+    }
+    f32x4 acc[RT][kFTPW];
+#pragma unroll
+    for (int i = 0; i < RT; ++i)
+#pragma unroll
+      for (int j = 0; j < kFTPW; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (h == 0)
+      fused_k_loop<RT, true>(acc, wt, lane, reinterpret_cast<const char*>(etile + rl * SE + 8 * kq), 16 * SE * 4, KC);
+    else
+      fused_k_loop<RT, false>(acc, wt, lane, reinterpret_cast<const char*>(atile + rl * SB + 8 * kq), 16 * SB * 2, KC);
+    __syncthreads();  // every wave has read the layer's input: the tile may be overwritten
+    // the lane-derived epilogue values are recomputed per layer: hoisted out of the layer loop they stay live across
+    // the K loops and spill
+    int lv = lane;
+    asm volatile("" : "+v"(lv));
+    const int erl = lv & 15, ekq = lv >> 4;
+    if (!last) {
+      // the columns behind the last tile that the next layer's last K step reads (an odd tile count): zeros
+      const int zw = q.KCN * 32 - NT * 16;  // 0 or 16
+      for (int i = tid; i < ROWS * zw; i += kFTH) {
+        const int b = i / zw;
+        atile[b * SB + NT * 16 + (i - b * zw)] = 0;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kFTPW; ++j) {
+      const int t = wave + kFW * j;
+      if (t >= NT) break;  // wave-uniform
+      const int n0 = t * 16 + 4 * ekq;
+      const f32x4 bq = *reinterpret_cast<const f32x4*>(p.mlp_b + (size_t)h * NT * 16 + n0);
+      f32x4 fq = {0.f, 0.f, 0.f, 0.f};
+      if (last) fq = *reinterpret_cast<const f32x4*>(p.fc + n0);
+#pragma unroll
+      for (int i = 0; i < RT; ++i) {
+        const int row = i * 16 + erl;
+        f32x4 v;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)  // padded neurons stay exactly 0
+          v[r] = n0 + r < p.N ? relu_keep_nan(acc[i][j][r] + bq[r]) : 0.f;
+        if (!last) {
+          *reinterpret_cast<u32x2*>(atile + row * SB + n0) = u32x2{cvt_pk_bf16(v[0], v[1]), cvt_pk_bf16(v[2], v[3])};
+        } else {  // uniform: every lane takes part in the shuffles
+          float d = 0.f;
+          d = fmaf(v[0], fq[0], d);
+          d = fmaf(v[1], fq[1], d);
+          d = fmaf(v[2], fq[2], d);
+          d = fmaf(v[3], fq[3], d);
+          d += __shfl_xor(d, 16);
+          d += __shfl_xor(d, 32);
+          if (lv < 16) part[row * NT + t] = d;
+        }
+      }
+    }
+    wl += (size_t)NT * KC * 64;
+    __syncthreads();
+  }
+
+  // ---- stage 4: logit[b] = (first_second[b] + the shares in tile order) + bias -----------------------------------------
+  if (tid < ROWS && b0 + tid < p.batch) {
+    const float* pp = part + tid * NT;
+    float deep = pp[0];
+    for (int t = 1; t < NT; ++t) deep += pp[t];
+    tr.out[b0 + tid] = (fs[tid] + deep) + p.bias[0];
+  }
+}
+
+template <int RT>
+hipError_t launch_rt(const FwdArgs& a, const Bf16FusedGeo& g, size_t lds, hipStream_t s) {
+  auto k = (a.flags & kHasQR) ? bf16_fused_kernel<RT, true> : bf16_fused_kernel<RT, false>;
+  const hipError_t e = ensure_lds_limit(reinterpret_cast<const void*>(k), lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k, dim3(fwd_grid(a, 16 * RT)), dim3(kFTH), lds, s, a, g);
+  return hipGetLastError();
+}
+
+inline int kc_of(int cols16) { return (cols16 * 16 + 31) / 32; }
+
+Bf16FusedGeo fused_geo(const uint16_t* wb, int NT, int NC0, int W0) {
+  Bf16FusedGeo g;
+  g.wb = wb;
+  g.KC0 = kc_of(NC0);
+  g.KCN = kc_of(NT);
+  g.WE = g.KC0 * 32 > W0 ? g.KC0 * 32 : (W0 + 7) & ~7;
+  g.SE = g.WE + 4;
+  g.SB = g.KCN * 32 + 8;
+  return g;
+}
+
+}  // namespace
+
+bool bf16_fused_supported(int F, int D, int H, int NT) { return D == 10 && F >= 1 && F <= kFMaxF && H >= 1 && NT >= 1 && NT <= kFW * kFTPW; }
+
+size_t bf16_fused_lds_bytes(int rows, int F, int D, int NT, int NC0, int W0) {
+  const Bf16FusedGeo g = fused_geo(nullptr, NT, NC0, W0);
+  return sizeof(float) * (size_t)fused_layout(rows, F, D, NT, g.SE, g.SB).total;
+}
+
+hipError_t launch_bf16_fused(const FwdArgs& a, const uint16_t* wb, int rows, hipStream_t s) {
+  if (!bf16_fused_supported(a.F, 10, a.H, a.NT) || a.batch <= 0) return hipErrorInvalidValue;
+  const Bf16FusedGeo g = fused_geo(wb, a.NT, a.NC0, a.W0);
+  const size_t lds = sizeof(float) * (size_t)fused_layout(rows, a.F, 10, a.NT, g.SE, g.SB).total;
+  if (lds > kFLdsMax) return hipErrorInvalidValue;
+  switch (rows) {
+    case 16: return launch_rt<1>(a, g, lds, s);
+    case 32: return launch_rt<2>(a, g, lds, s);
+    case 64: return launch_rt<4>(a, g, lds, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+}  // namespace dfwfm

@@ -14,6 +14,7 @@
 #include "dfwfm_internal.h"
 #include "../../include/dfwfm_serve.h"
 #include "../../include/dfwfm_bf16.h"
+#include "../../include/dfwfm_bf16_fused.h"
 #include "../../include/dfwfm_fold.h"
 
 using namespace dfwfm;
@@ -1034,6 +1035,108 @@ int dfwfm_bf16_forward(dfwfm_model* m, const int64_t* xi, int64_t xi_stride, con
   e = launch_bf16_mlp(ba, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, "bf16 MLP launch");
   return DFWFM_OK;
+}
+
+// The bf16 deep tower in one launch (include/dfwfm_bf16_fused.h, dfwfm_bf16_fused.hip)
+int dfwfm_bf16_fused_abi_version(void) { return DFWFM_BF16_FUSED_ABI_VERSION; }
+
+}  // extern "C"
+
+namespace {
+
+// the model's shape, and the gather launch's FwFM in the pieces form (a pair list sums in another order)
+bool fused_ok(const dfwfm_model* m) {
+  return m->cfg.use_deep && bf16_fused_supported(m->F, m->D, m->H, m->NT) && m->MT <= 3 && !(m->flags & kPairs) &&
+         bf16_fused_lds_bytes(16, m->F, m->D, m->NT, m->NC0, m->W0) <= 160 * 1024;
+}
+
+// Rows per workgroup for a launch of `rows` rows (the sums do not depend on it).  Every workgroup streams the whole
+// weight pack from L2 once, so a larger tile divides that traffic, but leaves CUs idle in a small launch.  Measured
+// (DESIGN.md section 3.12, 256 CUs): 16 rows win while they are at most one workgroup per CU (22.8 against 27.0 us at
+// 4096 rows), 32 rows from there on (30.4 against 34.1 at 8192, 184.9 against 286.0 at 81920); 64 rows (one workgroup
+// per CU by their LDS) never win (230.2 at 81920) and run only when forced: DFWFM_DIAG bf16rows=16 / 32 / 64 (tests,
+// A/B)
+int fused_rows(dfwfm_model* m, int64_t rows) {
+  const int forced = diag_opt("bf16rows", 0);
+  int64_t cus;
+  {  // the device's CUs (queried at the model's first call, so later calls are capturable into a graph)
+    std::lock_guard<std::mutex> lock(g_cu_mu);
+    if (m->dev_cus == 0) {
+      hipDeviceProp_t prop;
+      m->dev_cus = hipGetDeviceProperties(&prop, m->device) == hipSuccess ? prop.multiProcessorCount : 256;
+    }
+    cus = m->dev_cus;
+  }
+  auto fits = [&](int cand) { return bf16_fused_lds_bytes(cand, m->F, m->D, m->NT, m->NC0, m->W0) <= 160 * 1024; };
+  int r = 16;
+  if (forced == 32 || forced == 64) {
+    if (fits(forced)) r = forced;
+  } else if (forced == 0 && (rows + 15) / 16 > cus && fits(32)) {
+    r = 32;
+  }
+  return r;
+}
+
+int fused_check(dfwfm_model* m) {
+  if (!m->cfg.use_deep) return fail(DFWFM_ERR_UNSUPPORTED, "bf16 fused forward: the model has no deep tower");
+  if (!fused_ok(m))
+    return fail(DFWFM_ERR_UNSUPPORTED,
+                "bf16 fused forward: shape not supported (embedding_size 10, field_size <= 48, deep_nodes <= 512, no "
+                "FwFM pair list); use dfwfm_bf16_forward");
+  return DFWFM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dfwfm_bf16_fused_supported(dfwfm_model* m, int* supported) {
+  if (!m || !supported) return fail(DFWFM_ERR_INVALID_ARG, "null argument");
+  *supported = fused_ok(m) ? 1 : 0;
+  return DFWFM_OK;
+}
+
+int dfwfm_bf16_fused_forward_batches(dfwfm_model* m, int32_t nb, const int64_t* const* xi, int64_t xi_stride,
+                                     const float* const* xv, int64_t xv_stride, int64_t batch, float* const* out,
+                                     void* stream) {
+  if (!m) return fail(DFWFM_ERR_INVALID_ARG, "null model");
+  if (nb < 0) return fail(DFWFM_ERR_INVALID_ARG, "negative batch count");
+  int rc = fused_check(m);
+  if (rc != DFWFM_OK) return rc;
+  if (nb == 0) return DFWFM_OK;
+  if (!xi || !xv || !out) return fail(DFWFM_ERR_INVALID_ARG, "null pointer array");
+  for (int32_t i = 0; i < nb; ++i)
+    if ((rc = check_inputs(m, xi[i], xi_stride, xv[i], xv_stride, batch, out[i])) != DFWFM_OK) return rc;
+  if (!m->bf16_on)
+    return fail(DFWFM_ERR_STATE, "bf16 fused forward: the bf16 weight copy is absent or stale (dfwfm_model_pack_bf16)");
+  if (batch == 0) return DFWFM_OK;
+  // the tile for the first launch's rows (a set of up to kMaxSet batches); later launches of a larger set use it too
+  const int rows = fused_rows(m, (int64_t)(nb < kMaxSet ? nb : kMaxSet) * batch);
+  const int64_t tiles = (batch + rows - 1) / rows;
+  if ((int64_t)(nb < kMaxSet ? nb : kMaxSet) * tiles > 0x7fffffff)
+    return fail(DFWFM_ERR_UNSUPPORTED, "batch too large for the bf16 fused forward");
+  for (int32_t i0 = 0; i0 < nb; i0 += kMaxSet) {
+    const int32_t n = nb - i0 < kMaxSet ? nb - i0 : kMaxSet;
+    FwdArgs a;
+    fill_forward_args(m, a, xi[i0], xi_stride, xv[i0], xv_stride, batch, out[i0]);
+    if (n > 1) {
+      a.nb = n;
+      a.tiles = (int32_t)tiles;
+      for (int32_t j = 0; j < n; ++j) {
+        a.set_xi[j] = xi[i0 + j];
+        a.set_xv[j] = xv[i0 + j];
+        a.set_out[j] = out[i0 + j];
+      }
+    }
+    const hipError_t e = launch_bf16_fused(a, m->d_wbf16, rows, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "bf16 fused forward launch");
+  }
+  return DFWFM_OK;
+}
+
+int dfwfm_bf16_fused_forward(dfwfm_model* m, const int64_t* xi, int64_t xi_stride, const float* xv,
+                             int64_t xv_stride, int64_t batch, float* out, void* stream) {
+  return dfwfm_bf16_fused_forward_batches(m, 1, &xi, xi_stride, &xv, xv_stride, batch, &out, stream);
 }
 
 // The folded layer 1 of the fused inference forward (include/dfwfm_fold.h)

@@ -139,7 +139,8 @@ inline unsigned fwd_grid(const FwdArgs& a, int rows) {
 // they apply (product runs set none).  Keys: r32 (0 never / 1 always the 32-sample set kernel), ng (4: four-wave
 // forward / backward), ftrain (0: fwd_kernel<TRAIN> instead of the helper-wave training forward), part3 (0: the
 // generic kernel for MLP-free models), p3ng (4 / 8: MLP-free waves), bf16tile (0 / 1 / 2 / 3: the bf16 tower's tile per
-// wave, 16 x 16 / 16 x 80 / 32 x 80 / 32 x 80 with the weights in LDS; same logits), stamps / ring / ft / bwd / scatter /
+// wave, 16 x 16 / 16 x 80 / 32 x 80 / 32 x 80 with the weights in LDS; same logits), bf16rows (16 / 32 / 64: rows per
+// workgroup of the fused bf16 forward; same logits), stamps / ring / ft / bwd / scatter /
 // drop_flags (phase stamps and phase-skip bits; results invalid).  dflt when the key is absent.
 inline int diag_opt(const char* key, int dflt) {
   const char* s = getenv("DFWFM_DIAG");
@@ -433,6 +434,19 @@ size_t bf16_workspace_bytes(int NT, int NC0, int64_t batch);  // every region a 
 // bf16(W_l) of every hidden layer into `wb`, from the row-major f32 weights w[l] [N][K_l] (K_0 = K0, else N)
 hipError_t launch_bf16_pack(const float* const* w, uint16_t* wb, int H, int N, int K0, int NT, int NC0, hipStream_t s);
 hipError_t launch_bf16_mlp(const Bf16Args& a, hipStream_t s);
+
+// The same forward in one launch (dfwfm_bf16_fused.hip, include/dfwfm_bf16_fused.h): a workgroup carries `rows` (16,
+// 32 or 64) rows of one batch from Xi / Xv to the logits, the E tile and every activation in LDS; FwdArgs as for
+// dfwfm_forward (batch sets included), the weights from the pack of launch_bf16_pack.
+struct Bf16FusedGeo {
+  const uint16_t* wb;  // bf16 weight pack, per layer [NT][KC][64 lanes][8]
+  int32_t KC0, KCN;    // K steps of 32 of layer 1 and of the later layers
+  int32_t WE;          // f32 E tile columns that hold data or zeros (layer 1's K steps, the FwFM's padded fields)
+  int32_t SE, SB;      // LDS row strides: f32 E tile (floats), bf16 activation tile (bf16 elements)
+};
+bool bf16_fused_supported(int F, int D, int H, int NT);
+size_t bf16_fused_lds_bytes(int rows, int F, int D, int NT, int NC0, int W0);
+hipError_t launch_bf16_fused(const FwdArgs& a, const uint16_t* wb, int rows, hipStream_t s);
 
 // dW_l += G_l^T X_{l-1} and db_l += sum_b G_l for every layer in one launch.
 struct DwArgs {

@@ -74,6 +74,9 @@ class ForwardEngine:
         # forward() takes the bf16 deep tower (forward_bf16) for every B > 0, ahead of small_rows; the caller keeps
         # the bf16 weight copy current with sync_bf16 (DeepFMs sets it from its mlp_dtype)
         self.bf16 = False
+        # ... and its one-launch form (forward_bf16_fused) instead, when DeepFMs.bf16_fused asks for it and the shape
+        # is supported (DeepFMs sets it: bf16_fused and bf16_fused_supported())
+        self.bf16_fused = False
 
     def close(self):
         if self.handle is not None and self.handle.value:
@@ -211,7 +214,7 @@ class ForwardEngine:
     def forward(self, xi: torch.Tensor, xv: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
         B = xi.shape[0]
         if self.bf16 and B > 0:
-            return self.forward_bf16(xi, xv, out)
+            return self.forward_bf16_fused(xi, xv, out) if self.bf16_fused else self.forward_bf16(xi, xv, out)
         if 0 < B <= self.small_rows:
             return self.forward_small(xi, xv, out)
         ncat = self.cfg["field_size"] - self.cfg["numerical"]
@@ -298,14 +301,38 @@ class ForwardEngine:
             cache[B] = int(n.value)
         return cache[B]
 
-    def forward_batches(self, batches, outs) -> list:
-        """dfwfm_forward_batches: the forward of every (xi, xv) in `batches` (same batch size and row strides),
-        all in one launch per 32 batches; logits into outs[i], bit-identical to forward() on each batch alone."""
+    def bf16_fused_supported(self) -> bool:
+        """dfwfm_bf16_fused_supported: whether forward_bf16_fused / forward_bf16_batches run this model (its shape,
+        and no FwFM pair list on); host-only."""
+        v = ctypes.c_int(0)
+        _lib.check(_lib.lib().dfwfm_bf16_fused_supported(self.handle, ctypes.byref(v)), "dfwfm_bf16_fused_supported")
+        return bool(v.value)
+
+    def forward_bf16_fused(self, xi: torch.Tensor, xv: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+        """dfwfm_bf16_fused_forward (include/dfwfm_bf16_fused.h): forward_bf16 in one launch and without a workspace,
+        after sync_bf16(True); the same bits.  DfwfmError for a shape bf16_fused_supported() refuses."""
+        B = xi.shape[0]
+        ncat = self.cfg["field_size"] - self.cfg["numerical"]
+        num = self.cfg["numerical"]
+        _require_rows(xi, "Xi", torch.int64, self.device, ncat)
+        _require_rows(xv, "Xv", torch.float32, self.device, num)
+        if out is None:
+            out = torch.empty(B, dtype=torch.float32, device=self.device)
+        elif out.numel() < B:
+            raise ValueError("forward_bf16_fused: output smaller than the batch")
+        xs = xi.stride(0) if ncat > 0 else 0
+        vs = xv.stride(0) if num > 0 else 0
+        rc = _lib.lib().dfwfm_bf16_fused_forward(self.handle, ctypes.c_void_p(xi.data_ptr()), xs,
+                                                 ctypes.c_void_p(xv.data_ptr()), vs, B,
+                                                 ctypes.c_void_p(out.data_ptr()), _stream_handle(self.device))
+        _lib.check(rc, "dfwfm_bf16_fused_forward")
+        return out
+
+    def _batch_set_args(self, batches, outs, what):
+        """The argument checks of a batch set: (nb, B, xs, vs, pxi, pxv, pout) for the C call."""
         nb = len(batches)
-        if nb == 0:
-            return outs
         if len(outs) != nb:
-            raise ValueError("forward_batches: one output per batch")
+            raise ValueError(f"{what}: one output per batch")
         ncat = self.cfg["field_size"] - self.cfg["numerical"]
         num = self.cfg["numerical"]
         xi0, xv0 = batches[0]
@@ -316,14 +343,33 @@ class ForwardEngine:
             _require_rows(xi, "Xi", torch.int64, self.device, ncat)
             _require_rows(xv, "Xv", torch.float32, self.device, num)
             if xi.shape[0] != B or (ncat > 0 and xi.stride(0) != xs) or (num > 0 and xv.stride(0) != vs):
-                raise ValueError("forward_batches: every batch needs the same size and row strides")
+                raise ValueError(f"{what}: every batch needs the same size and row strides")
         for o in outs:
             if o.numel() < B:
-                raise ValueError("forward_batches: output smaller than the batch")
+                raise ValueError(f"{what}: output smaller than the batch")
         P = ctypes.c_void_p * nb
         pxi = P(*[xi.data_ptr() for xi, _ in batches])
         pxv = P(*[xv.data_ptr() for _, xv in batches])
         pout = P(*[o.data_ptr() for o in outs])
+        return nb, B, xs, vs, pxi, pxv, pout
+
+    def forward_bf16_batches(self, batches, outs) -> list:
+        """dfwfm_bf16_fused_forward_batches: forward_bf16_fused of every (xi, xv) in `batches` (same batch size and row
+        strides), one launch per 32 batches; logits into outs[i], bit-identical to forward_bf16 on each batch alone."""
+        if len(batches) == 0:
+            return outs
+        nb, B, xs, vs, pxi, pxv, pout = self._batch_set_args(batches, outs, "forward_bf16_batches")
+        rc = _lib.lib().dfwfm_bf16_fused_forward_batches(self.handle, nb, pxi, xs, pxv, vs, B, pout,
+                                                         _stream_handle(self.device))
+        _lib.check(rc, "dfwfm_bf16_fused_forward_batches")
+        return outs
+
+    def forward_batches(self, batches, outs) -> list:
+        """dfwfm_forward_batches: the forward of every (xi, xv) in `batches` (same batch size and row strides),
+        all in one launch per 32 batches; logits into outs[i], bit-identical to forward() on each batch alone."""
+        if len(batches) == 0:
+            return outs
+        nb, B, xs, vs, pxi, pxv, pout = self._batch_set_args(batches, outs, "forward_batches")
         rc = _lib.lib().dfwfm_forward_batches(self.handle, nb, pxi, xs, pxv, vs, B, pout, _stream_handle(self.device))
         _lib.check(rc, "dfwfm_forward_batches")
         return outs
