@@ -22,7 +22,9 @@ forward_batches_4096_us (per call) and forward_batches_4096_us_per_batch in the 
 --bf16-fused (implies --bf16): the one-launch bf16 forward (eng.forward_bf16_fused, include/dfwfm_bf16_fused.h) beside
 eng.forward and eng.forward_bf16 in the same process, under models["deepfwfm_bf16_fused"]; and the batch-set leg also
 through eng.forward_bf16_batches: forward_bf16_batches_4096_us and forward_bf16_batches_4096_us_per_batch in that row
-(81920 rows: 20 resident batches of 4096, beside forward_batches_4096_us_per_batch of the f32 row).
+(81920 rows: 20 resident batches of 4096, beside forward_batches_4096_us_per_batch of the f32 row).  The same calls
+with the numerical fields folded into layer 1 (eng.sync_bf16_fold, include/dfwfm_bf16_fold.h) are measured right
+behind the unfolded ones at every batch, same figures, under models["deepfwfm_bf16_fused_fold"].
 """
 import argparse
 import json
@@ -137,11 +139,25 @@ def main():
                    "(data/results/criteo.md:5)", "calls": a.calls, "models": {}}
     for name, deep in (("deepfwfm", 1), ("fwfm", 0)):
         m, sizes = build(deep, dev)
-        rows, small, bf16, fused = {}, {}, {}, {}
+        rows, small, bf16, fused, folded = {}, {}, {}, {}, {}
         with torch.no_grad():
             eng = m._sync_engine(dev)
             if a.bf16 and deep:
                 eng.sync_bf16(True)
+            num_tabs = [m.fm_2nd_embeddings[f].weight.detach() for f in range(13)]
+
+            def fold(on):  # the folded layer 1 of the fused bf16 forward on / off (one pack launch)
+                if eng.sync_bf16_fold(num_tabs, on) != on:
+                    raise RuntimeError("the model did not fold")
+
+            def stats(fwd, dst, b, xi, xv, out, calls):
+                r = measure(fwd, xi, xv, out, calls, dev)
+                r["samples_per_s_one_call_at_a_time"] = round(b / (r["device_us_median"] * 1e-6), 1)
+                if deep and (dst is rows or dst is small):  # f32 MFMA fraction of the back-to-back rate (967,620 FLOP per sample, 157.3 TF/s)
+                    r["mfma_frac_back_to_back"] = round(967620 * b / (r["back_to_back_us"] * 1e-6) / 157.3e12, 4)
+                if dst is bf16 or dst is fused or dst is folded:  # the tower alone (952,800 FLOP per sample of the unfolded tower) against the bf16 MFMA peak
+                    r["bf16_mfma_frac_back_to_back"] = round(952800 * b / (r["back_to_back_us"] * 1e-6) / 2.5e15, 4)
+                dst[str(b)] = r
             for b in batches:
                 xi, xv = synth.synth_inputs(sizes, 13, b, seed=7)
                 xi, xv = torch.from_numpy(xi).to(dev), torch.from_numpy(xv).to(dev)
@@ -150,13 +166,11 @@ def main():
                 for fwd, dst in ((eng.forward, rows),) + (((eng.forward_small, small),) if a.small and deep else ()) \
                         + (((eng.forward_bf16, bf16),) if a.bf16 and deep else ()) \
                         + (((eng.forward_bf16_fused, fused),) if a.bf16_fused and deep else ()):
-                    r = measure(fwd, xi, xv, out, calls, dev)
-                    r["samples_per_s_one_call_at_a_time"] = round(b / (r["device_us_median"] * 1e-6), 1)
-                    if deep and dst is not bf16 and dst is not fused:  # f32 MFMA fraction of the back-to-back rate (967,620 FLOP per sample, 157.3 TF/s)
-                        r["mfma_frac_back_to_back"] = round(967620 * b / (r["back_to_back_us"] * 1e-6) / 157.3e12, 4)
-                    if dst is bf16 or dst is fused:  # the tower alone (952,800 FLOP per sample) against the bf16 MFMA peak
-                        r["bf16_mfma_frac_back_to_back"] = round(952800 * b / (r["back_to_back_us"] * 1e-6) / 2.5e15, 4)
-                    dst[str(b)] = r
+                    stats(fwd, dst, b, xi, xv, out, calls)
+                if a.bf16_fused and deep:
+                    fold(True)
+                    stats(eng.forward_bf16_fused, folded, b, xi, xv, out, calls)
+                    fold(False)
                 if a.bf16 and deep and b >= 8192 and b % 4096 == 0:
                     t, nb = measure_batch_set(eng.forward_batches, xi, xv, out, dev)
                     rows[str(b)]["forward_batches_4096_us"] = round(t, 2)
@@ -165,11 +179,18 @@ def main():
                         t, nb = measure_batch_set(eng.forward_bf16_batches, xi, xv, out, dev)
                         fused[str(b)]["forward_bf16_batches_4096_us"] = round(t, 2)
                         fused[str(b)]["forward_bf16_batches_4096_us_per_batch"] = round(t / nb, 2)
+                        fold(True)
+                        t, nb = measure_batch_set(eng.forward_bf16_batches, xi, xv, out, dev)
+                        fold(False)
+                        folded[str(b)]["forward_bf16_batches_4096_us"] = round(t, 2)
+                        folded[str(b)]["forward_bf16_batches_4096_us_per_batch"] = round(t / nb, 2)
         res["models"][name] = rows
         if bf16:
             res["models"][name + "_bf16"] = bf16
         if fused:
             res["models"][name + "_bf16_fused"] = fused
+        if folded:
+            res["models"][name + "_bf16_fused_fold"] = folded
         if small:
             res["models"][name + "_small"] = small
     print(json.dumps(res))

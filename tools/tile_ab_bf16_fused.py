@@ -1,9 +1,11 @@
 """A/B of the fused bf16 forward's row tile (DFWFM_DIAG bf16rows=16|32|64) in one process: Criteo-39 DeepFwFM,
 back-to-back time per call from 20-call graphs beside eng.forward and eng.forward_bf16, every form's logits compared
 with forward_bf16's (equal bits), and at 81920 rows the 20-batch set through forward_batches / forward_bf16_batches.
-Prints a line per batch size, then one JSON line.
+Prints a line per batch size, then one JSON line.  --fold: the fused forms with the numerical fields folded into layer 1
+(include/dfwfm_bf16_fold.h); their logits are then compared with one another (the folded contract is not the per-layer
+path's).
 
-  python tools/tile_ab_bf16_fused.py [--batches 256,1024,4096,8192,16384,32768,81920]
+  python tools/tile_ab_bf16_fused.py [--batches 256,1024,4096,8192,16384,32768,81920] [--fold]
 """
 import argparse
 import json
@@ -49,6 +51,7 @@ def forced(rows):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", default="256,1024,4096,8192,16384,32768,81920")
+    ap.add_argument("--fold", action="store_true", help="the fused forms with the folded layer 1 (eng.sync_bf16_fold)")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
@@ -58,6 +61,8 @@ def main():
     with torch.no_grad():
         eng = m._sync_engine(dev)
         eng.sync_bf16(True)
+        if a.fold and not eng.sync_bf16_fold([m.fm_2nd_embeddings[f].weight.detach() for f in range(13)], True):
+            raise RuntimeError("the model did not fold")
         for b in [int(x) for x in a.batches.split(",")]:
             xi, xv = synth.synth_inputs(sizes, 13, b, seed=7)
             xi, xv = torch.from_numpy(xi).to(dev), torch.from_numpy(xv).to(dev)
@@ -65,7 +70,7 @@ def main():
             forced(0)
             row = {"f32": back_to_back_us(lambda: eng.forward(xi, xv, out), dev),
                    "bf16": back_to_back_us(lambda: eng.forward_bf16(xi, xv, out), dev)}
-            ref = eng.forward_bf16(xi, xv).clone()
+            ref = (eng.forward_bf16_fused if a.fold else eng.forward_bf16)(xi, xv).clone()
             for t in (16, 32, 64):
                 forced(t)
                 row[f"fused{t}"] = back_to_back_us(lambda: eng.forward_bf16_fused(xi, xv, out), dev)

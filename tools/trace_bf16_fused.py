@@ -1,7 +1,9 @@
 """Workload for a kernel trace of the three forwards side by side (run it under `rocprofv3 --kernel-trace --stats`):
 Criteo-39 DeepFwFM, eager calls of eng.forward, eng.forward_bf16 and eng.forward_bf16_fused at one batch size, then
 20-batch sets of 4096 rows through eng.forward_batches and eng.forward_bf16_batches.  One batch size per process, so
-the per-kernel averages of the trace belong to that size.
+the per-kernel averages of the trace belong to that size.  --fold: the fused calls run with the numerical fields
+folded into layer 1 (include/dfwfm_bf16_fold.h; the kernel's name is the same, so folded and unfolded are runs of
+their own).
 
   rocprofv3 --kernel-trace --stats -d OUT -o run --output-format csv -- python3 tools/trace_bf16_fused.py --batch 4096
 """
@@ -23,6 +25,7 @@ def main():
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--sets", type=int, default=0, help="20-batch sets of 4096 rows through both batch-set calls")
+    ap.add_argument("--fold", action="store_true", help="the fused calls with the folded layer 1 (eng.sync_bf16_fold)")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
@@ -31,6 +34,8 @@ def main():
     with torch.no_grad():
         eng = m._sync_engine(dev)
         eng.sync_bf16(True)
+        if a.fold and not eng.sync_bf16_fold([m.fm_2nd_embeddings[f].weight.detach() for f in range(13)], True):
+            raise RuntimeError("the model did not fold")
         xi, xv = synth.synth_inputs(sizes, 13, a.batch, seed=7)
         xi, xv = torch.from_numpy(xi).to(dev), torch.from_numpy(xv).to(dev)
         out = torch.empty(a.batch, dtype=torch.float32, device=dev)

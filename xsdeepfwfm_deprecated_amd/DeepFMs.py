@@ -128,6 +128,12 @@ class DeepFMs(nn.Module):
         # full batches as batch sets of it -- the same logits bit for bit.  Off by default; a shape the fused kernel does
         # not support (ForwardEngine.bf16_fused_supported) silently keeps the per-layer path
         self.bf16_fused = False
+        # with mlp_dtype = "bf16" and bf16_fused on a supported shape: the numerical fields folded into layer 1 of the
+        # one-launch bf16 forward (Xv * bf16(P), P = W1 v_f[0] rebuilt after each weight update: 9 K steps of 32 instead
+        # of 13 at Criteo-39; include/dfwfm_bf16_fold.h).  Another rounding of the same size:
+        # the logits are no longer the per-layer path's bits.  Off by default; a model that cannot fold (no numerical
+        # field, a tile that would not fit) silently stays unfolded
+        self.bf16_fold = False
         # the device backward's gradient sums in a fixed order (dfwfm_set_deterministic; like
         # torch.use_deterministic_algorithms): two runs of a training step give the same bits, at ~+7 us (+2.6 %) per
         # step at Criteo-39 (sorted table scatter, split-K slices); on by default, False: float atomics (arrival order)
@@ -290,6 +296,9 @@ class DeepFMs(nn.Module):
             eng.small_rows = max(int(getattr(self, "small_batch_rows", 0)), 0) if self.use_deep else 0
             eng.bf16 = eng.sync_bf16(self._mlp_bf16()) if self.use_deep else False
             eng.bf16_fused = bool(eng.bf16 and getattr(self, "bf16_fused", False) and eng.bf16_fused_supported())
+            if eng.bf16:  # the fused form's folded layer 1, rebuilt when W1, a numerical table or the bf16 copy changed
+                eng.sync_bf16_fold([second[f].weight.detach() for f in range(self.num)],
+                                   bool(eng.bf16_fused and getattr(self, "bf16_fold", False)))
         return eng
 
     def _mlp_bf16(self) -> bool:

@@ -39,7 +39,8 @@ def _units():
     return u
 HEADERS = ["dfwfm_internal.h", "dfwfm_device.h", os.path.join("..", "..", "include", "dfwfm.h"),
            os.path.join("..", "..", "include", "dfwfm_serve.h"), os.path.join("..", "..", "include", "dfwfm_bf16.h"),
-           os.path.join("..", "..", "include", "dfwfm_bf16_fused.h"), os.path.join("..", "..", "include", "dfwfm_fold.h")]
+           os.path.join("..", "..", "include", "dfwfm_bf16_fused.h"), os.path.join("..", "..", "include", "dfwfm_fold.h"),
+           os.path.join("..", "..", "include", "dfwfm_bf16_fold.h")]
 ARCH = os.environ.get("DFWFM_OFFLOAD_ARCH", "gfx950")
 CPU_PATH = os.path.join(PKG_DIR, "libdfwfm_cpu.so")
 CPU_SOURCES = ["dfwfm_cpu.cpp"]
@@ -186,6 +187,13 @@ BF16_FUSED_SIGNATURES = {
 FOLD_SIGNATURES = {
     "dfwfm_fold_abi_version": (ctypes.c_int, []),
     "dfwfm_model_fold_numerical": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), _P]),
+}
+
+# the folded layer 1 of the one-launch bf16 forward (include/dfwfm_bf16_fold.h): same library, its own header and ABI
+# version
+BF16_FOLD_SIGNATURES = {
+    "dfwfm_bf16_fold_abi_version": (ctypes.c_int, []),
+    "dfwfm_model_fold_bf16": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), _P]),
 }
 
 _lib = None
@@ -405,6 +413,12 @@ def lib():
             fn.argtypes = args
         if L.dfwfm_fold_abi_version() != 1:
             raise DfwfmError("libdfwfm fold ABI mismatch")
+        for name, (res, args) in BF16_FOLD_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        if L.dfwfm_bf16_fold_abi_version() != 1:
+            raise DfwfmError("libdfwfm bf16 fold ABI mismatch")
         _lib = L
     return _lib
 

@@ -72,6 +72,9 @@ def get_parser():
     a("-bf16_fused", default=0, type=int, choices=[0, 1],
       help="with -mlp_dtype bf16: the bf16 forward as one launch, and batch sets of it in the evaluation "
            "(DeepFMs.bf16_fused; the same logits; an unsupported shape keeps the per-layer path)")
+    a("-bf16_fold", default=0, type=int, choices=[0, 1],
+      help="with -mlp_dtype bf16 -bf16_fused 1: the numerical fields folded into layer 1 of the one-launch bf16 "
+           "forward (DeepFMs.bf16_fold; another rounding of the same size; a model that cannot fold stays unfolded)")
     return p
 
 
@@ -121,4 +124,5 @@ def get_model(cuda, feature_sizes, pars, dynamic_quantization=False, static_quan
                 logger=logger)
     m.mlp_dtype = getattr(pars, "mlp_dtype", "f32")  # a CPU model with "bf16" raises at its first forward
     m.bf16_fused = bool(getattr(pars, "bf16_fused", 0))
+    m.bf16_fold = bool(getattr(pars, "bf16_fold", 0))
     return m

@@ -24,6 +24,13 @@
 // SB = 8 mod 16 bf16: the 16 rows a quarter wave reads 16 bytes of start 16 bytes apart modulo 256, no bank conflict.
 // Rows past the batch hold zeros and run through every stage (every wave reaches every barrier); nothing of them is
 // written out.
+//
+// The folded layer 1 (include/dfwfm_bf16_fold.h, the FOLD forms): a tile row is [xsh floats unused][E: F D][Xv: num]
+// [zeros], xsh = (-num D) mod 4, so that the categorical block at column num D starts 16-byte aligned; the gather's
+// numerical rows also store their Xv behind column F D, and layer 1 reads its K steps from column num D on against the
+// fragments of bf16_fold_pack_kernel (categorical columns of bf16(W1) | bf16(P) | zeros).  xsh + WE is a multiple of 8,
+// so SE = 4 mod 8 still.  The FwFM then clamps its padded fields to F (Xv lies where field F would).  Layers 2..H, the
+// shallow half and the unfolded forms are untouched.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -139,8 +146,9 @@ __device__ __forceinline__ void fused_k_loop(f32x4 (&acc)[RT][kFTPW], const u32x
 }
 
 // RT: 16-row sub-tiles per workgroup; QR: some field may be a QR embedding (false: the gather carries no second
-// operand)
-template <int RT, bool QR>
+// operand); FOLD: layer 1 folded (include/dfwfm_bf16_fold.h) -- a form of its own, so that the unfolded one keeps its
+// code (and registers) exactly
+template <int RT, bool QR, bool FOLD>
 __global__ void __launch_bounds__(kFTH) __attribute__((amdgpu_waves_per_eu(RT == 4 ? 2 : 4)))
 bf16_fused_kernel(const FwdArgs p, const Bf16FusedGeo q) {
   constexpr int D = 10;
@@ -158,8 +166,9 @@ bf16_fused_kernel(const FwdArgs p, const Bf16FusedGeo q) {
   const int flags = p.flags;
   const int Fp = r4(F);
   const int SE = q.SE, SB = q.SB;
+  const int xsh = FOLD ? q.xsh : 0, k0 = FOLD ? q.k0 : 0, nxv = FOLD ? q.nxv : 0;
   const FusedLds L = fused_layout(ROWS, F, D, p.NT, SE, SB);
-  float* etile = smem + L.tile;
+  float* etile = smem + L.tile + xsh;  // (the folded layer 1: the categorical block 16-byte aligned)
   uint16_t* atile = reinterpret_cast<uint16_t*>(smem + L.tile);
   float* fs = smem + L.fs;
   FieldDev* desc = reinterpret_cast<FieldDev*>(smem + L.desc);
@@ -178,7 +187,8 @@ bf16_fused_kernel(const FwdArgs p, const Bf16FusedGeo q) {
     for (int i = tid; i < F * D; i += kFTH) fwlw_s[i] = p.fwlw[i];
   if ((flags & kFoLw) && tid < F) lw_s[tid] = p.lw[tid];
   {
-    // columns [F D, WE): layer 1 reads K steps of 32 up to KC0 * 32, the FwFM fields up to 4 S
+    // columns [F D, WE): layer 1 reads K steps of 32 up to k0 + KC0 * 32, the FwFM fields up to 4 S (the folded
+    // layer 1's Xv columns are among them: the gather's numerical rows write them after the barrier)
     const int zc = F * D;
     const int w = q.WE - zc;
     for (int i = tid; i < ROWS * w; i += kFTH) {
@@ -295,6 +305,7 @@ bf16_fused_kernel(const FwdArgs p, const Bf16FusedGeo q) {
             for (int d = 0; d < D; ++d)
               e[d] = live[k] ? combine(mode[k], va[k][d], QR ? vb[QR ? k : 0][d] : 0.f, scale[k]) : 0.f;
             store_row<D>(etile + b * SE + f * D, e);
+            if (FOLD && f < nxv) etile[b * SE + F * D + f] = live[k] ? scale[k] : 0.f;  // the folded layer 1's K row
           }
           fo[b * Fp + f] = live[k] ? combine(mode[k], fa[k], QR ? fb[QR ? k : 0] : 0.f, scale[k]) : 0.f;
         }
@@ -345,7 +356,8 @@ bf16_fused_kernel(const FwdArgs p, const Bf16FusedGeo q) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           const int s = s0 + u;
-          bv[u] = s < S ? ecol[(4 * s + (lane >> 4)) * D] : 0.f;
+          const int l = 4 * s + (lane >> 4);  // (the columns of fields past F are zeros; folded, Xv lies there)
+          bv[u] = (s < S && (!FOLD || l < F)) ? ecol[l * D] : 0.f;
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u)
@@ -398,7 +410,7 @@ bf16_fused_kernel(const FwdArgs p, const Bf16FusedGeo q) {
   // ---- stages 2 and 3: the hidden layers; the tile is read by every wave's K loop, then overwritten in place ----------
   const int rl = lane & 15, kq = lane >> 4;
   const int NT = p.NT;
-  const u32x4* wl = reinterpret_cast<const u32x4*>(q.wb);
+  const u32x4* wl = reinterpret_cast<const u32x4*>(q.w1);
   for (int h = 0; h < p.H; ++h) {
     const bool last = h == p.H - 1;
     const int KC = h == 0 ? q.KC0 : q.KCN;
@@ -415,7 +427,8 @@ bf16_fused_kernel(const FwdArgs p, const Bf16FusedGeo q) {
 #pragma unroll
       for (int j = 0; j < kFTPW; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     if (h == 0)
-      fused_k_loop<RT, true>(acc, wt, lane, reinterpret_cast<const char*>(etile + rl * SE + 8 * kq), 16 * SE * 4, KC);
+      fused_k_loop<RT, true>(acc, wt, lane, reinterpret_cast<const char*>(etile + rl * SE + k0 + 8 * kq), 16 * SE * 4,
+                               KC);
     else
       fused_k_loop<RT, false>(acc, wt, lane, reinterpret_cast<const char*>(atile + rl * SB + 8 * kq), 16 * SB * 2, KC);
     __syncthreads();  // every wave has read the layer's input: the tile may be overwritten
@@ -461,7 +474,10 @@ bf16_fused_kernel(const FwdArgs p, const Bf16FusedGeo q) {
         }
       }
     }
-    wl += (size_t)NT * KC * 64;
+    if (FOLD && h == 0)
+      wl = reinterpret_cast<const u32x4*>(q.wn);  // layer 1's fragments were the folded ones, not the pack's
+    else
+      wl += (size_t)NT * KC * 64;
     __syncthreads();
   }
 
@@ -474,9 +490,48 @@ bf16_fused_kernel(const FwdArgs p, const Bf16FusedGeo q) {
   }
 }
 
+// dfwfm_model_fold_bf16: layer 1's fragments in the order of dfwfm_model_pack_bf16 over the folded K rows, one thread
+// per (tile, K step, lane) and its 8 weights of neuron n = 16 t + (l & 15), rows k = 32 c + 8 (l >> 4) + j:
+//   k < (F - num) D          bf16(W1[n][num D + k])                         (the categorical columns, field order)
+//   k < (F - num) D + num    bf16(P[f][n]), P[f][n] = sum_d W1[n][f D + d] v_f[0][d], f = k - (F - num) D: the
+//                            products are exact in f64, summed in f64 over d = 0..D-1 in that order, rounded to f32
+//   else, and n >= N         0
+__global__ void __launch_bounds__(256) bf16_fold_pack_kernel(const float* __restrict__ w1,
+                                                             const FieldDev* __restrict__ fields,
+                                                             u32x4* __restrict__ dst, int N, int F, int D, int num,
+                                                             int KC, int64_t total) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int lane = (int)(i & 63);
+  const int64_t tc = i >> 6;
+  const int c = (int)(tc % KC);
+  const int n = (int)(tc / KC) * 16 + (lane & 15);
+  const int k0 = c * 32 + 8 * (lane >> 4);
+  const int K = F * D;
+  const int KCat = (F - num) * D;
+  float v[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int k = k0 + j;
+    v[j] = 0.f;
+    if (n < N && k < KCat) {
+      v[j] = w1[(size_t)n * K + num * D + k];
+    } else if (n < N && k < KCat + num) {
+      const int f = k - KCat;
+      const float* w = w1 + (size_t)n * K + f * D;
+      const float* e = fields[f].emb2;
+      double acc = 0.0;
+      for (int d = 0; d < D; ++d) acc += (double)w[d] * (double)e[d];
+      v[j] = (float)acc;
+    }
+  }
+  dst[i] = u32x4{cvt_pk_bf16(v[0], v[1]), cvt_pk_bf16(v[2], v[3]), cvt_pk_bf16(v[4], v[5]), cvt_pk_bf16(v[6], v[7])};
+}
+
 template <int RT>
 hipError_t launch_rt(const FwdArgs& a, const Bf16FusedGeo& g, size_t lds, hipStream_t s) {
-  auto k = (a.flags & kHasQR) ? bf16_fused_kernel<RT, true> : bf16_fused_kernel<RT, false>;
+  auto k = g.nxv ? ((a.flags & kHasQR) ? bf16_fused_kernel<RT, true, true> : bf16_fused_kernel<RT, false, true>)
+                 : ((a.flags & kHasQR) ? bf16_fused_kernel<RT, true, false> : bf16_fused_kernel<RT, false, false>);
   const hipError_t e = ensure_lds_limit(reinterpret_cast<const void*>(k), lds);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k, dim3(fwd_grid(a, 16 * RT)), dim3(kFTH), lds, s, a, g);
@@ -485,13 +540,18 @@ hipError_t launch_rt(const FwdArgs& a, const Bf16FusedGeo& g, size_t lds, hipStr
 
 inline int kc_of(int cols16) { return (cols16 * 16 + 31) / 32; }
 
-Bf16FusedGeo fused_geo(const uint16_t* wb, int NT, int NC0, int W0) {
+// fold: the geometry of the folded layer 1 (include/dfwfm_bf16_fold.h); the pointers are the caller's to fill
+Bf16FusedGeo fused_geo(int F, int num, int D, int NT, int NC0, int W0, bool fold) {
   Bf16FusedGeo g;
-  g.wb = wb;
-  g.KC0 = kc_of(NC0);
+  g.w1 = g.wn = nullptr;
+  g.KC0 = fold ? bf16_fold_steps(F, num, D) : kc_of(NC0);
   g.KCN = kc_of(NT);
-  g.WE = g.KC0 * 32 > W0 ? g.KC0 * 32 : (W0 + 7) & ~7;
-  g.SE = g.WE + 4;
+  g.xsh = fold ? (4 - (num * D) % 4) % 4 : 0;
+  g.k0 = fold ? num * D : 0;
+  g.nxv = fold ? num : 0;
+  const int need = g.k0 + g.KC0 * 32 > W0 ? g.k0 + g.KC0 * 32 : W0;
+  g.WE = ((g.xsh + need + 7) & ~7) - g.xsh;  // the row's floats, xsh + WE, a multiple of 8: SE = 4 mod 8
+  g.SE = g.xsh + g.WE + 4;
   g.SB = g.KCN * 32 + 8;
   return g;
 }
@@ -500,14 +560,16 @@ Bf16FusedGeo fused_geo(const uint16_t* wb, int NT, int NC0, int W0) {
 
 bool bf16_fused_supported(int F, int D, int H, int NT) { return D == 10 && F >= 1 && F <= kFMaxF && H >= 1 && NT >= 1 && NT <= kFW * kFTPW; }
 
-size_t bf16_fused_lds_bytes(int rows, int F, int D, int NT, int NC0, int W0) {
-  const Bf16FusedGeo g = fused_geo(nullptr, NT, NC0, W0);
+size_t bf16_fused_lds_bytes(int rows, int F, int num, int D, int NT, int NC0, int W0, bool fold) {
+  const Bf16FusedGeo g = fused_geo(F, num, D, NT, NC0, W0, fold);
   return sizeof(float) * (size_t)fused_layout(rows, F, D, NT, g.SE, g.SB).total;
 }
 
-hipError_t launch_bf16_fused(const FwdArgs& a, const uint16_t* wb, int rows, hipStream_t s) {
+hipError_t launch_bf16_fused(const FwdArgs& a, const uint16_t* wb, const uint16_t* wfold, int rows, hipStream_t s) {
   if (!bf16_fused_supported(a.F, 10, a.H, a.NT) || a.batch <= 0) return hipErrorInvalidValue;
-  const Bf16FusedGeo g = fused_geo(wb, a.NT, a.NC0, a.W0);
+  Bf16FusedGeo g = fused_geo(a.F, a.num, 10, a.NT, a.NC0, a.W0, wfold != nullptr);
+  g.w1 = wfold ? wfold : wb;
+  g.wn = wb + (size_t)a.NT * kc_of(a.NC0) * 64 * 8;  // behind the pack's unfolded layer 1
   const size_t lds = sizeof(float) * (size_t)fused_layout(rows, a.F, 10, a.NT, g.SE, g.SB).total;
   if (lds > kFLdsMax) return hipErrorInvalidValue;
   switch (rows) {
@@ -516,6 +578,16 @@ hipError_t launch_bf16_fused(const FwdArgs& a, const uint16_t* wb, int rows, hip
     case 64: return launch_rt<4>(a, g, lds, s);
     default: return hipErrorInvalidValue;
   }
+}
+
+hipError_t launch_bf16_fold_pack(const float* w1, const FieldDev* fields, uint16_t* dst, int N, int F, int D, int num,
+                                 int NT, hipStream_t s) {
+  const int KC = bf16_fold_steps(F, num, D);
+  const int64_t total = (int64_t)NT * KC * 64;
+  if (total <= 0) return hipSuccess;
+  hipLaunchKernelGGL(bf16_fold_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w1, fields,
+                     reinterpret_cast<u32x4*>(dst), N, F, D, num, KC, total);
+  return hipGetLastError();
 }
 
 }  // namespace dfwfm

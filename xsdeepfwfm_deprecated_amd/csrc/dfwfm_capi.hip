@@ -14,6 +14,7 @@
 #include "dfwfm_internal.h"
 #include "../../include/dfwfm_serve.h"
 #include "../../include/dfwfm_bf16.h"
+#include "../../include/dfwfm_bf16_fold.h"
 #include "../../include/dfwfm_bf16_fused.h"
 #include "../../include/dfwfm_fold.h"
 
@@ -66,6 +67,9 @@ struct dfwfm_model {
   float* d_bias;   // [1]
   uint16_t* d_wbf16;  // dfwfm_model_pack_bf16: bf16 copy of the hidden layers' weights in MFMA operand order
   bool bf16_on;       // the copy matches the dense parameters set (cleared by set_dense)
+  // dfwfm_model_fold_bf16 (include/dfwfm_bf16_fold.h): layer 1's folded bf16 fragments [NT][bf16_fold_steps][64][8]
+  uint16_t* d_wbf16f;
+  bool bf16fold_on;   // they match the parameters, the tables and the copy (cleared by set_dense / set_tables / pack_bf16)
   // dfwfm_model_fold_numerical (include/dfwfm_fold.h): layer 1's folded forward fragments [NT][foldNC][64]
   int foldNC;          // chunks of the folded pack (0: this model never folds)
   int foldSX, foldW0;  // the folded tile's row stride and valid columns past the E tile's start
@@ -154,7 +158,7 @@ void free_model(dfwfm_model* m) {
   void* ptrs[] = {m->d_fields, m->d_upack, m->d_err,     m->d_wpack, m->d_mlp_b,   m->d_fc,  m->d_fwlw,
                   m->d_lw,     m->d_bias,  m->d_stamps,  m->d_wtpack, m->d_rsk,   m->d_ws,
                   m->d_ell,    m->d_cnt,   m->d_spstat, m->d_pairs, m->d_pkrows, m->d_pk,
-                  m->d_wbf16};
+                  m->d_wbf16,  m->d_wbf16f};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   delete m;
@@ -407,6 +411,7 @@ int dfwfm_model_set_tables(dfwfm_model* m, const dfwfm_field_tables* t, int32_t 
   memcpy(m->h_fields, host, sizeof(FieldDev) * n);
   m->pkw = 0;  // the serving copy was built from the old tables
   m->fold_on = false;  // and so was the folded layer 1 (the numerical tables' row 0)
+  m->bf16fold_on = false;
   m->flags &= ~kHasQR;
   for (int f = 0; f < n; ++f)
     if (host[f].c > 0) m->flags |= kHasQR;
@@ -485,6 +490,7 @@ static int set_dense_impl(dfwfm_model* m, const float* field_cov, const float* f
   m->sp = 0;  // new weights: the sparse tower's ELL is stale until rebuilt
   m->bf16_on = false;  // and the bf16 copy until dfwfm_model_pack_bf16
   m->fold_on = false;  // and the folded layer 1 until dfwfm_model_fold_numerical
+  m->bf16fold_on = false;  // ... of the bf16 tower until dfwfm_model_fold_bf16
   m->flags &= ~kPairs;  // and so is the FwFM pair list
   for (int h = 0; h < m->H; ++h) m->lin_w[h] = lin_w ? lin_w[h] : nullptr;
   return DFWFM_OK;
@@ -960,6 +966,7 @@ int dfwfm_bf16_abi_version(void) { return DFWFM_BF16_ABI_VERSION; }
 int dfwfm_model_pack_bf16(dfwfm_model* m, int enable, void* stream) {
   if (!m) return fail(DFWFM_ERR_INVALID_ARG, "null model");
   m->bf16_on = false;
+  m->bf16fold_on = false;  // the folded layer 1 goes with the copy (dfwfm_model_fold_bf16)
   if (!enable) return DFWFM_OK;  // the buffer is kept for the next enable and freed with the model (hipFree syncs)
   if (!m->cfg.use_deep) return fail(DFWFM_ERR_UNSUPPORTED, "bf16 pack: the model has no deep tower");
   if (!m->dense_set) return fail(DFWFM_ERR_STATE, "set_dense must precede pack_bf16");
@@ -1047,7 +1054,12 @@ namespace {
 // the model's shape, and the gather launch's FwFM in the pieces form (a pair list sums in another order)
 bool fused_ok(const dfwfm_model* m) {
   return m->cfg.use_deep && bf16_fused_supported(m->F, m->D, m->H, m->NT) && m->MT <= 3 && !(m->flags & kPairs) &&
-         bf16_fused_lds_bytes(16, m->F, m->D, m->NT, m->NC0, m->W0) <= 160 * 1024;
+         bf16_fused_lds_bytes(16, m->F, m->num, m->D, m->NT, m->NC0, m->W0, false) <= 160 * 1024;
+}
+
+// the LDS of a row-tile form of the model as it runs: with the folded layer 1 or without
+size_t fused_lds(const dfwfm_model* m, int rows, bool fold) {
+  return bf16_fused_lds_bytes(rows, m->F, m->num, m->D, m->NT, m->NC0, m->W0, fold);
 }
 
 // Rows per workgroup for a launch of `rows` rows (the sums do not depend on it).  Every workgroup streams the whole
@@ -1067,7 +1079,7 @@ int fused_rows(dfwfm_model* m, int64_t rows) {
     }
     cus = m->dev_cus;
   }
-  auto fits = [&](int cand) { return bf16_fused_lds_bytes(cand, m->F, m->D, m->NT, m->NC0, m->W0) <= 160 * 1024; };
+  auto fits = [&](int cand) { return fused_lds(m, cand, m->bf16fold_on) <= 160 * 1024; };
   int r = 16;
   if (forced == 32 || forced == 64) {
     if (fits(forced)) r = forced;
@@ -1128,7 +1140,8 @@ int dfwfm_bf16_fused_forward_batches(dfwfm_model* m, int32_t nb, const int64_t* 
         a.set_out[j] = out[i0 + j];
       }
     }
-    const hipError_t e = launch_bf16_fused(a, m->d_wbf16, rows, (hipStream_t)stream);
+    const hipError_t e = launch_bf16_fused(a, m->d_wbf16, m->bf16fold_on ? m->d_wbf16f : nullptr, rows,
+                                           (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "bf16 fused forward launch");
   }
   return DFWFM_OK;
@@ -1137,6 +1150,39 @@ int dfwfm_bf16_fused_forward_batches(dfwfm_model* m, int32_t nb, const int64_t* 
 int dfwfm_bf16_fused_forward(dfwfm_model* m, const int64_t* xi, int64_t xi_stride, const float* xv,
                              int64_t xv_stride, int64_t batch, float* out, void* stream) {
   return dfwfm_bf16_fused_forward_batches(m, 1, &xi, xi_stride, &xv, xv_stride, batch, &out, stream);
+}
+
+// The folded layer 1 of the one-launch bf16 forward (include/dfwfm_bf16_fold.h)
+int dfwfm_bf16_fold_abi_version(void) { return DFWFM_BF16_FOLD_ABI_VERSION; }
+
+int dfwfm_model_fold_bf16(dfwfm_model* m, int32_t enable, int32_t* enabled, void* stream) {
+  if (!m || !enabled) return fail(DFWFM_ERR_INVALID_ARG, "null argument");
+  *enabled = 0;
+  m->bf16fold_on = false;
+  // a model that never folds: no deep tower, no numerical field, or not one the fused calls run
+  if (!enable || !m->cfg.use_deep || m->num == 0 || !fused_ok(m)) return DFWFM_OK;
+  if (!m->tables_set || !m->dense_set)
+    return fail(DFWFM_ERR_STATE, "set_tables and set_dense must precede fold_bf16");
+  if (!m->bf16_on)
+    return fail(DFWFM_ERR_STATE, "fold_bf16: the bf16 weight copy is absent or stale (dfwfm_model_pack_bf16)");
+  // every row-tile form keeps fitting, and the 16- and 32-row forms keep their second workgroup per CU (80 KB each)
+  for (int rows = 16; rows <= 64; rows *= 2) {
+    const size_t u = fused_lds(m, rows, false), f = fused_lds(m, rows, true);
+    if ((u <= 160 * 1024 && f > 160 * 1024) || (rows < 64 && u <= 80 * 1024 && f > 80 * 1024)) return DFWFM_OK;
+  }
+  if (!m->lin_w[0] || diag_opt("bf16fold", 1) == 0) return DFWFM_OK;  // DFWFM_DIAG bf16fold=0: forced off
+  if (!m->d_wbf16f) {
+    int rc = dev_alloc(&m->d_wbf16f, (size_t)m->NT * bf16_fold_steps(m->F, m->num, m->D) * 64 * 8);
+    if (rc != DFWFM_OK) return rc;
+  }
+  // the sources travel as kernel arguments (W1 of the last set_dense, the device field descriptors of the last
+  // set_tables): nothing staged from the stack, no synchronisation
+  hipError_t e = launch_bf16_fold_pack(m->lin_w[0], m->d_fields, m->d_wbf16f, m->N, m->F, m->D, m->num, m->NT,
+                                       (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "bf16 fold pack launch");
+  m->bf16fold_on = true;
+  *enabled = 1;
+  return DFWFM_OK;
 }
 
 // The folded layer 1 of the fused inference forward (include/dfwfm_fold.h)

@@ -140,7 +140,8 @@ inline unsigned fwd_grid(const FwdArgs& a, int rows) {
 // forward / backward), ftrain (0: fwd_kernel<TRAIN> instead of the helper-wave training forward), part3 (0: the
 // generic kernel for MLP-free models), p3ng (4 / 8: MLP-free waves), bf16tile (0 / 1 / 2 / 3: the bf16 tower's tile per
 // wave, 16 x 16 / 16 x 80 / 32 x 80 / 32 x 80 with the weights in LDS; same logits), bf16rows (16 / 32 / 64: rows per
-// workgroup of the fused bf16 forward; same logits), stamps / ring / ft / bwd / scatter /
+// workgroup of the fused bf16 forward; same logits), bf16fold (0: dfwfm_model_fold_bf16 leaves the fused bf16 forward
+// unfolded), stamps / ring / ft / bwd / scatter /
 // drop_flags (phase stamps and phase-skip bits; results invalid).  dflt when the key is absent.
 inline int diag_opt(const char* key, int dflt) {
   const char* s = getenv("DFWFM_DIAG");
@@ -438,15 +439,28 @@ hipError_t launch_bf16_mlp(const Bf16Args& a, hipStream_t s);
 // The same forward in one launch (dfwfm_bf16_fused.hip, include/dfwfm_bf16_fused.h): a workgroup carries `rows` (16,
 // 32 or 64) rows of one batch from Xi / Xv to the logits, the E tile and every activation in LDS; FwdArgs as for
 // dfwfm_forward (batch sets included), the weights from the pack of launch_bf16_pack.
+// With the folded layer 1 (include/dfwfm_bf16_fold.h, `wfold` below non-null / `fold` true) layer 1 reads its own
+// fragments over the K rows (categorical columns | Xv | zeros), and a tile row is [xsh unused floats][E: F D][Xv: num]
+// [zeros]: xsh = (-num D) mod 4 floats start the categorical block 16-byte aligned.
 struct Bf16FusedGeo {
-  const uint16_t* wb;  // bf16 weight pack, per layer [NT][KC][64 lanes][8]
-  int32_t KC0, KCN;    // K steps of 32 of layer 1 and of the later layers
+  const uint16_t* w1;  // layer 1's bf16 fragments [NT][KC0][64 lanes][8]: of the pack, or the folded ones
+  const uint16_t* wn;  // layers 2..H of the pack, per layer [NT][KCN][64 lanes][8]
+  int32_t KC0, KCN;    // K steps of 32 of layer 1 (as it runs) and of the later layers
   int32_t WE;          // f32 E tile columns that hold data or zeros (layer 1's K steps, the FwFM's padded fields)
   int32_t SE, SB;      // LDS row strides: f32 E tile (floats), bf16 activation tile (bf16 elements)
+  int32_t xsh;         // floats the E tile's rows start behind the row's base (0 unfolded)
+  int32_t k0;          // E tile column of layer 1's first K row (0 unfolded, num D folded)
+  int32_t nxv;         // numerical fields whose Xv the gather stores behind column F D (0 unfolded)
 };
 bool bf16_fused_supported(int F, int D, int H, int NT);
-size_t bf16_fused_lds_bytes(int rows, int F, int D, int NT, int NC0, int W0);
-hipError_t launch_bf16_fused(const FwdArgs& a, const uint16_t* wb, int rows, hipStream_t s);
+inline int bf16_fold_steps(int F, int num, int D) { return ((F - num) * D + num + 31) / 32; }
+size_t bf16_fused_lds_bytes(int rows, int F, int num, int D, int NT, int NC0, int W0, bool fold);
+// wfold: layer 1's folded fragments (launch_bf16_fold_pack), or null: unfolded
+hipError_t launch_bf16_fused(const FwdArgs& a, const uint16_t* wb, const uint16_t* wfold, int rows, hipStream_t s);
+// dfwfm_model_fold_bf16: layer 1's folded fragments [NT][bf16_fold_steps][64 lanes][8 bf16] from W1 [N][F D] and row 0
+// of the numerical fields' second-order tables (the device descriptors)
+hipError_t launch_bf16_fold_pack(const float* w1, const FieldDev* fields, uint16_t* dst, int N, int F, int D, int num,
+                                 int NT, hipStream_t s);
 
 // dW_l += G_l^T X_{l-1} and db_l += sum_b G_l for every layer in one launch.
 struct DwArgs {

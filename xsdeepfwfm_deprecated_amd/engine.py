@@ -108,6 +108,7 @@ class ForwardEngine:
                                                      _stream_handle(self.device)), "dfwfm_model_set_tables")
         self._packed_key = None  # set_tables drops the serving copy
         self._fold_key = None  # ... and turns the folded layer 1 off
+        self._bf16_fold_key = None  # ... and the bf16 tower's
         self._keep = arr
         self._tables_key = key
 
@@ -138,6 +139,7 @@ class ForwardEngine:
         self._sparse_key = None
         self._bf16_key = None
         self._fold_key = None  # the folded layer 1: built from W1 and the numerical tables' row 0
+        self._bf16_fold_key = None  # ... and the bf16 tower's (sync_bf16_fold)
 
     def sync_fold(self, tables, enable: bool = True) -> bool:
         """dfwfm_model_fold_numerical (include/dfwfm_fold.h): (re)build the folded layer 1 of the fused inference
@@ -208,7 +210,23 @@ class ForwardEngine:
         _lib.check(_lib.lib().dfwfm_model_pack_bf16(self.handle, int(bool(enable)), _stream_handle(self.device)),
                    "dfwfm_model_pack_bf16")
         self._bf16_key = key
+        self._bf16_fold_key = None  # dfwfm_model_pack_bf16 turns the folded layer 1 off
         return bool(enable)
+
+    def sync_bf16_fold(self, tables, enable: bool = True) -> bool:
+        """dfwfm_model_fold_bf16 (include/dfwfm_bf16_fold.h): (re)build the folded layer 1 of forward_bf16_fused /
+        forward_bf16_batches after a weight update or a sync_bf16 (stream-ordered, no host synchronisation), or turn
+        it off.  tables: the numerical fields' second-order tables (row 0 is folded into layer 1).  Call it after
+        sync_bf16(True).  Returns whether the fold is on (False for a model that never folds)."""
+        key = (self._dense_key, tuple((t.data_ptr(), t._version) for t in tables), bool(enable))
+        if key == getattr(self, "_bf16_fold_key", None):
+            return self._bf16_fold_on
+        en = ctypes.c_int32(0)
+        _lib.check(_lib.lib().dfwfm_model_fold_bf16(self.handle, int(bool(enable)), ctypes.byref(en),
+                                                    _stream_handle(self.device)), "dfwfm_model_fold_bf16")
+        self._bf16_fold_on = bool(en.value)
+        self._bf16_fold_key = key
+        return self._bf16_fold_on
 
     # -- hot path ----------------------------------------------------------
     def forward(self, xi: torch.Tensor, xv: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
