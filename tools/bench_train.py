@@ -48,6 +48,9 @@ def main():
     ap.add_argument("--steps-per-graph", type=int, default=1,
                     help="fused, one rank: K > 1 replays K consecutive steps over the resident ring as one graph "
                          "(FusedTrainStep.step_many; --steps must be a multiple of K)")
+    ap.add_argument("--lazy-adam", action="store_true",
+                    help="fused, one rank: the categorical tables' Adam over the rows each batch touched only "
+                         "(FusedTrainStep(lazy_table_adam=True); not the reference's dense semantics)")
     ap.add_argument("--gpus", type=int, default=1, help="ranks (one process per GPU; started here unless "
                                                            "torchrun already set WORLD_SIZE)")
     a = ap.parse_args()
@@ -96,7 +99,7 @@ def main():
         # the four resident batches are read in place (one captured graph set each), like a loader's ring of
         # device input buffers; --copy-inputs copies each batch into the step's own buffers first
         trainer = FusedTrainStep(model, B, lr=1e-3, weight_decay=3e-7, dist=dist, resident_inputs=not a.copy_inputs,
-                                 deterministic=not a.atomic)
+                                 deterministic=not a.atomic, lazy_table_adam=a.lazy_adam)
 
     def step(i):
         xi, xv, y = batches[i % 4]
@@ -145,7 +148,11 @@ def main():
            "first_order": a.first_order, "dropout": not a.no_dropout, "wall_s": round(wall, 3),
            "host_enqueue_us_per_step": round(host * 1e6 / a.steps, 1),
            "mode": a.mode, "deterministic": not a.atomic, "steps_per_graph": K, "inputs": "copied" if (a.copy_inputs or a.mode != "fused") else "resident (read in place)",
+           "lazy_adam": bool(trainer is not None and getattr(trainer, "lazy", False)),
            "final_loss_sum": round(float(loss.item()), 4)}
+    if res["lazy_adam"]:
+        # distinct rows the four resident batches touch per step, per table family (what the lazy step updates)
+        res["touched_rows_per_step"] = touched_rows(model, [b[0] for b in batches])
     if trainer is not None and getattr(trainer, "sparse", False):
         # touched-row lists all-gathered per step (fixed capacity: sum over tables of min(batch, rows))
         res["exchange"] = {"backend": torch.distributed.get_backend(), "packed_bytes_per_rank": trainer.sp_bytes,
@@ -157,6 +164,36 @@ def main():
         print(json.dumps(res), flush=True)
     if world > 1 or a.exchange_world1:
         torch.distributed.destroy_process_group()
+
+
+def touched_rows(model, xis):
+    """Distinct table rows per step over the batches' keys: second-order (width D) and first-order (width 1) tables
+    (a QR field counts its quotient and its remainder rows), averaged over the batches; and the tables' total rows."""
+    fields, _ = model._param_layout()
+    per = []
+    for xi in xis:
+        n2 = n1 = 0
+        for f in range(model.num, model.field_size):
+            e2, e2r, e1, e1r = fields[f]
+            k = xi[:, f - model.num]
+            for q, r, fam in ((e2, e2r, 2), (e1, e1r, 1)):
+                if q is None:
+                    continue
+                if r is None:
+                    cnt = int(torch.unique(k).numel())
+                else:
+                    c = int(r.shape[0])
+                    cnt = int(torch.unique(k // c).numel()) + int(torch.unique(k % c).numel())
+                if fam == 2:
+                    n2 += cnt
+                else:
+                    n1 += cnt
+        per.append((n2, n1))
+    rows = lambda i: sum(int(t.shape[0]) for f in range(model.num, model.field_size)  # noqa: E731
+                         for t in fields[f][i:i + 2] if t is not None)
+    return {"second_order": round(sum(p[0] for p in per) / len(per), 1),
+            "first_order": round(sum(p[1] for p in per) / len(per), 1),
+            "second_order_table_rows": rows(0), "first_order_table_rows": rows(2)}
 
 
 def apply_bench(trainer, model, sizes, B, dev, worlds, reps=50):

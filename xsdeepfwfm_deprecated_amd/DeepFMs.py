@@ -138,6 +138,12 @@ class DeepFMs(nn.Module):
         # torch.use_deterministic_algorithms): two runs of a training step give the same bits, at ~+7 us (+2.6 %) per
         # step at Criteo-39 (sorted table scatter, split-K slices); on by default, False: float atomics (arrival order)
         self.deterministic = True
+        # fit()'s fused Adam step updates only the rows of the categorical tables that each batch touched
+        # (FusedTrainStep(lazy_table_adam=True), include/dfwfm_lazy_adam.h): torch.optim.SparseAdam / LazyAdam
+        # semantics -- an untouched row gets no moment decay and no L2 that step -- which are NOT the reference's dense
+        # Adam, so the training goldens do not cover it.  Off by default; fit() raises ValueError when it is set and
+        # the fused step is not the path (a CPU module, another optimizer, a teacher model, fused_fit off)
+        self.lazy_table_adam = False
         self._defer_index_check = 0     # >0 inside a batched caller: one flag read at its end, not per batch
         self._engine = None
 

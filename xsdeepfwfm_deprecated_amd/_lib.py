@@ -24,7 +24,8 @@ LIB_PATH = os.path.join(PKG_DIR, "libdfwfm.so")
 # A/B of build variants only (e.g. libdfwfm_ns4.so built with DFWFM_HIPCC_FLAGS=-DDFWFM_NSETS=4)
 LOAD_PATH = os.path.join(PKG_DIR, os.environ["DFWFM_LIB"]) if os.environ.get("DFWFM_LIB") else LIB_PATH
 SOURCES = ["dfwfm_kernels.hip", "dfwfm_fwd32.hip", "dfwfm_ftrain.hip", "dfwfm_train.hip", "dfwfm_prune.hip", "dfwfm_metrics.hip", "dfwfm_sparse.hip",
-           "dfwfm_spmlp.hip", "dfwfm_serve.hip", "dfwfm_bf16.hip", "dfwfm_bf16_fused.hip", "dfwfm_capi.hip"]
+           "dfwfm_spmlp.hip", "dfwfm_serve.hip", "dfwfm_bf16.hip", "dfwfm_bf16_fused.hip", "dfwfm_lazy_adam.hip",
+           "dfwfm_capi.hip"]
 # the forward / backward kernel templates are instantiated once per embedding size, each size in its own
 # translation unit (-DDFWFM_KD=<D>) so they compile in parallel; the plain object holds everything else
 EMB_SIZES = (4, 8, 10, 16, 32)
@@ -37,10 +38,11 @@ def _units():
     for s in PER_D_SOURCES:
         u += [(s, f"{os.path.splitext(s)[0]}_d{d}.o", [f"-DDFWFM_KD={d}"]) for d in EMB_SIZES]
     return u
-HEADERS = ["dfwfm_internal.h", "dfwfm_device.h", os.path.join("..", "..", "include", "dfwfm.h"),
+HEADERS = ["dfwfm_internal.h", "dfwfm_device.h", "dfwfm_adam.h", os.path.join("..", "..", "include", "dfwfm.h"),
            os.path.join("..", "..", "include", "dfwfm_serve.h"), os.path.join("..", "..", "include", "dfwfm_bf16.h"),
            os.path.join("..", "..", "include", "dfwfm_bf16_fused.h"), os.path.join("..", "..", "include", "dfwfm_fold.h"),
-           os.path.join("..", "..", "include", "dfwfm_bf16_fold.h")]
+           os.path.join("..", "..", "include", "dfwfm_bf16_fold.h"),
+           os.path.join("..", "..", "include", "dfwfm_lazy_adam.h")]
 ARCH = os.environ.get("DFWFM_OFFLOAD_ARCH", "gfx950")
 CPU_PATH = os.path.join(PKG_DIR, "libdfwfm_cpu.so")
 CPU_SOURCES = ["dfwfm_cpu.cpp"]
@@ -54,6 +56,7 @@ STATUS = {0: "ok", -1: "invalid argument", -2: "unsupported", -3: "HIP error", -
 FLAG_INDEX_OUT_OF_RANGE = 1
 BWD_TABLES, BWD_MLP_WEIGHTS, BWD_TILES, BWD_SPREAD, BWD_REDUCE, BWD_SCATTER = 1, 2, 4, 8, 16, 32  # dfwfm_backward_phases
 FAMILY_SECOND, FAMILY_FIRST = 0, 1  # dfwfm_sparse_grads_local
+LAZY_PLAIN, LAZY_QUOTIENT, LAZY_REMAINDER = 0, 1, 2  # dfwfm_lazy_adam_table.kind
 ADAM_STATE_BYTES = 48
 
 
@@ -92,6 +95,13 @@ class dfwfm_grads(ctypes.Structure):
 class dfwfm_adam_tensor(ctypes.Structure):
     _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p),
                 ("exp_avg_sq", ctypes.c_void_p), ("numel", ctypes.c_int64)]
+
+
+class dfwfm_lazy_adam_table(ctypes.Structure):
+    _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p),
+                ("exp_avg_sq", ctypes.c_void_p), ("stamp", ctypes.c_void_p), ("rows", ctypes.c_int64),
+                ("key_range", ctypes.c_int64), ("c", ctypes.c_int64), ("width", ctypes.c_int32),
+                ("column", ctypes.c_int32), ("kind", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 class dfwfm_sparse_dest(ctypes.Structure):
@@ -194,6 +204,15 @@ FOLD_SIGNATURES = {
 BF16_FOLD_SIGNATURES = {
     "dfwfm_bf16_fold_abi_version": (ctypes.c_int, []),
     "dfwfm_model_fold_bf16": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), _P]),
+}
+
+# the row-lazy Adam step of the categorical tables (include/dfwfm_lazy_adam.h): same library, its own header and ABI
+# version
+LAZY_ADAM_SIGNATURES = {
+    "dfwfm_lazy_adam_abi_version": (ctypes.c_int, []),
+    "dfwfm_lazy_adam_step_dev": (ctypes.c_int, [ctypes.POINTER(dfwfm_lazy_adam_table), ctypes.c_int32, _P,
+                                                ctypes.c_int64, ctypes.c_int64, ctypes.c_double, ctypes.c_double,
+                                                ctypes.c_double, ctypes.c_double, ctypes.c_double, _P, _P]),
 }
 
 _lib = None
@@ -419,6 +438,12 @@ def lib():
             fn.argtypes = args
         if L.dfwfm_bf16_fold_abi_version() != 1:
             raise DfwfmError("libdfwfm bf16 fold ABI mismatch")
+        for name, (res, args) in LAZY_ADAM_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        if L.dfwfm_lazy_adam_abi_version() != 1:
+            raise DfwfmError("libdfwfm lazy Adam ABI mismatch")
         _lib = L
     return _lib
 

@@ -75,6 +75,10 @@ def get_parser():
     a("-bf16_fold", default=0, type=int, choices=[0, 1],
       help="with -mlp_dtype bf16 -bf16_fused 1: the numerical fields folded into layer 1 of the one-launch bf16 "
            "forward (DeepFMs.bf16_fold; another rounding of the same size; a model that cannot fold stays unfolded)")
+    a("-lazy_adam", default=0, type=int, choices=[0, 1],
+      help="training on a HIP device with Adam: the categorical tables' Adam updates only the rows each batch touched "
+           "(DeepFMs.lazy_table_adam; SparseAdam / LazyAdam semantics, NOT the reference's dense Adam: untouched rows "
+           "get no moment decay and no L2)")
     return p
 
 
@@ -125,4 +129,5 @@ def get_model(cuda, feature_sizes, pars, dynamic_quantization=False, static_quan
     m.mlp_dtype = getattr(pars, "mlp_dtype", "f32")  # a CPU model with "bf16" raises at its first forward
     m.bf16_fused = bool(getattr(pars, "bf16_fused", 0))
     m.bf16_fold = bool(getattr(pars, "bf16_fold", 0))
+    m.lazy_table_adam = bool(getattr(pars, "lazy_adam", 0))  # fit() raises if the fused Adam step is not the path
     return m

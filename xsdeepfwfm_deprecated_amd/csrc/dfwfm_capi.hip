@@ -17,6 +17,7 @@
 #include "../../include/dfwfm_bf16_fold.h"
 #include "../../include/dfwfm_bf16_fused.h"
 #include "../../include/dfwfm_fold.h"
+#include "../../include/dfwfm_lazy_adam.h"
 
 using namespace dfwfm;
 
@@ -1999,6 +2000,80 @@ int dfwfm_adam_step_dev(const dfwfm_adam_tensor* t, int32_t n, double lr, double
   if (keep.empty()) {
     hipError_t e = launch_adam_dev(list, 1, st, h, true, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "adam launch");
+  }
+  return DFWFM_OK;
+}
+
+int dfwfm_lazy_adam_abi_version(void) { return DFWFM_LAZY_ADAM_ABI_VERSION; }
+
+int dfwfm_lazy_adam_step_dev(const dfwfm_lazy_adam_table* t, int32_t n, const int64_t* xi, int64_t xi_stride,
+                             int64_t batch, double lr, double beta1, double beta2, double eps, double weight_decay,
+                             void* state_dev, void* stream) {
+  if (!state_dev) return fail(DFWFM_ERR_INVALID_ARG, "null state block");
+  if (n < 0) return fail(DFWFM_ERR_INVALID_ARG, "negative table count");
+  if (batch < 0) return fail(DFWFM_ERR_INVALID_ARG, "negative batch");
+  if (n > 0 && !t) return fail(DFWFM_ERR_INVALID_ARG, "null table array");
+  if (batch > 0 && n > 0 && (!xi || xi_stride < 1)) return fail(DFWFM_ERR_INVALID_ARG, "null xi or xi_stride < 1");
+  for (int i = 0; i < n; ++i) {
+    const dfwfm_lazy_adam_table& x = t[i];
+    if (!x.param || !x.grad || !x.exp_avg || !x.exp_avg_sq || !x.stamp)
+      return fail(DFWFM_ERR_INVALID_ARG, "lazy table %d: null pointer", i);
+    if (x.rows < 1 || x.width < 1 || x.key_range < 1)
+      return fail(DFWFM_ERR_INVALID_ARG, "lazy table %d: rows, width and key_range must be >= 1", i);
+    if (x.column < 0 || (batch > 0 && x.column >= xi_stride))
+      return fail(DFWFM_ERR_INVALID_ARG, "lazy table %d: column %d outside xi's %lld", i, x.column, (long long)xi_stride);
+    if (x.kind != DFWFM_LAZY_PLAIN && x.kind != DFWFM_LAZY_QUOTIENT && x.kind != DFWFM_LAZY_REMAINDER)
+      return fail(DFWFM_ERR_INVALID_ARG, "lazy table %d: kind %d", i, x.kind);
+    if (x.kind != DFWFM_LAZY_PLAIN && x.c < 1) return fail(DFWFM_ERR_INVALID_ARG, "lazy table %d: c < 1 on a QR kind", i);
+    // every key of [0, key_range) must land on a row of the table: the kernel indexes without a row count
+    const int64_t top = x.kind == DFWFM_LAZY_PLAIN ? x.key_range - 1
+                        : x.kind == DFWFM_LAZY_QUOTIENT ? (x.key_range - 1) / x.c
+                                                        : (x.c < x.key_range ? x.c : x.key_range) - 1;
+    if (top >= x.rows)
+      return fail(DFWFM_ERR_INVALID_ARG, "lazy table %d: key range %lld reaches row %lld of %lld", i,
+                  (long long)x.key_range, (long long)top, (long long)x.rows);
+    if (lazy_blocks(x.width, batch) > 0x3fffffff) return fail(DFWFM_ERR_UNSUPPORTED, "lazy table %d: batch too large", i);
+  }
+  LazyArgs a;
+  memset(&a, 0, sizeof a);
+  a.xi = xi;
+  a.xi_stride = xi_stride;
+  a.batch = batch;
+  a.st = reinterpret_cast<AdamDevState*>(state_dev);
+  a.h = AdamHyper{lr, beta1, beta2, eps, weight_decay};
+  // the tables' launches (<= kLazyList tables each); the last one advances the device step counter (without a table
+  // or a sample it is one empty workgroup)
+  LazyList list;
+  memset(&list, 0, sizeof list);
+  const int nt = batch > 0 ? n : 0;
+  int64_t blocks = 0;
+  for (int i = 0; i <= nt; ++i) {
+    const bool last = i == nt;
+    const int64_t nb = last ? 0 : lazy_blocks(t[i].width, batch);
+    if (last || list.n == kLazyList || blocks + nb > 0x7fffffff) {
+      a.bump = last ? 1 : 0;
+      a.nblocks = (int32_t)blocks;
+      hipError_t e = launch_lazy_adam(list, a, (hipStream_t)stream);
+      if (e != hipSuccess) return hip_fail(e, "lazy adam launch");
+      list.n = 0;
+      blocks = 0;
+    }
+    if (last) break;
+    const dfwfm_lazy_adam_table& x = t[i];
+    LazyTable& d = list.t[list.n];
+    d.p = x.param;
+    d.g = x.grad;
+    d.m = x.exp_avg;
+    d.v = x.exp_avg_sq;
+    d.stamp = x.stamp;
+    d.key_range = x.key_range;
+    d.c = x.c;
+    d.width = x.width;
+    d.column = x.column;
+    d.kind = x.kind;
+    d.block0 = (int32_t)blocks;
+    ++list.n;
+    blocks += nb;
   }
   return DFWFM_OK;
 }

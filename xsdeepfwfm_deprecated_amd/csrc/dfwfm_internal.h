@@ -636,4 +636,40 @@ hipError_t launch_adam_dev(const AdamList& list, int total_blocks, AdamDevState*
 hipError_t launch_bce_grad(const float* z, const float* y, int64_t n, float denom, float* dz, float* loss_sum,
                            hipStream_t s);
 
+// The row-lazy Adam step (include/dfwfm_lazy_adam.h, dfwfm_lazy_adam.hip): one table of a launch.  The host has
+// checked that every key of [0, key_range) maps to a row of the table, so the kernel indexes without a row count.
+struct LazyTable {
+  float* p;
+  float* g;
+  float* m;
+  float* v;
+  int32_t* stamp;
+  int64_t key_range;
+  int64_t c;
+  int32_t width, column, kind;
+  int32_t block0;  // first work block of the table (a block = 256 samples)
+};
+constexpr int kLazyList = 54;  // tables per launch (the list is a kernel argument, < 4 KiB with LazyArgs)
+struct LazyList {
+  LazyTable t[kLazyList];
+  int32_t n;
+};
+struct LazyArgs {
+  const int64_t* xi;
+  int64_t xi_stride, batch;
+  AdamDevState* st;
+  AdamHyper h;
+  int32_t bump, nblocks;
+};
+static_assert(sizeof(LazyList) + sizeof(LazyArgs) + 64 <= 4096, "lazy Adam launch arguments over 4 KiB");
+constexpr int kLazyGroup = 16;   // lanes that update one owned row of a table wider than one float
+constexpr int kLazyRounds = 8;   // distinct rows per wave that elect one claimant among their samples
+// work blocks of one table for `batch` samples: 256 samples each, one lane per sample
+inline int64_t lazy_blocks(int width, int64_t batch) {
+  (void)width;
+  return (batch + 255) / 256;
+}
+// one launch; with `bump` (the call's last launch) the last workgroup to finish advances the counter
+hipError_t launch_lazy_adam(const LazyList& list, const LazyArgs& a, hipStream_t s);
+
 }  // namespace dfwfm

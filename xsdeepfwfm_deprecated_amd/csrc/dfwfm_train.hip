@@ -18,6 +18,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "dfwfm_adam.h"
 #include "dfwfm_device.h"
 #include "dfwfm_internal.h"
 
@@ -1629,28 +1630,14 @@ __global__ void __launch_bounds__(64 * NW) dwr_reduce_kernel(DwArgs a, RedArgs r
 }
 
 // ---------------------------------------------------------------------------
-// Adam (torch.optim.Adam, single-tensor form, torch/optim/adam.py _single_tensor_adam):
-// g += wd * p; m = lerp(m, g, 1 - b1);
-// v = v * b2 + (1 - b2) * g * g; p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)
+// Adam (torch.optim.Adam): the per-element arithmetic (adam_elem) and the step's scalars (adam_coef) are in
+// dfwfm_adam.h, shared with the row-lazy kernel (dfwfm_lazy_adam.hip)
 // ---------------------------------------------------------------------------
-// one element of torch.optim.Adam: torch's CPU kernels' evaluation order -- fmadd where ATen's vector path
-// uses one, every other product / sum rounded on its own
-struct AdamCoef {
-  float step_size, omb1, b2, omb2, eps, wd, bc2_sqrt;
-};
-__device__ __forceinline__ void adam_elem(const AdamCoef& c, float& p, float g, float& m, float& v) {
-  if (c.wd != 0.f) g = fmaf(c.wd, p, g);                          // grad.add(param, alpha=wd): ATen's fmadd
-  m = fmaf(c.omb1, __fsub_rn(g, m), m);                            // exp_avg.lerp_(grad, 1-b1): fmadd, w < 0.5
-  v = __fmul_rn(v, c.b2);                                          // exp_avg_sq.mul_(b2)
-  v = __fadd_rn(v, __fmul_rn(__fmul_rn(c.omb2, g), g));           //   .addcmul_(g, g, 1-b2)
-  const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(v), c.bc2_sqrt), c.eps);  // sqrt(v)/sqrt(bc2) + eps
-  p = __fadd_rn(p, __fdiv_rn(__fmul_rn(-c.step_size, m), denom));  // addcdiv_(m, denom, -lr/bc1)
-}
-
 // a block's kAdamBlock (4096) elements: when the tensor's four arrays are 16-byte aligned thread t owns the four
 // float4 [4t + 1024u, 4t + 1024u + 4), u < 4 -- all sixteen 16-byte loads issued before any update (bytes in flight
 // for HBM), three 16-byte stores each -- else the lanes take consecutive elements
-template <typename TList>
+// (EW: the form of the second moment's sum on the element-wise paths, dfwfm_adam.h)
+template <int EW, typename TList>
 __device__ __forceinline__ void adam_block(const TList& list, const AdamCoef& c, int bid) {
   if (list.n <= 0) return;
   int lo = 0, hi = list.n - 1;
@@ -1666,7 +1653,7 @@ __device__ __forceinline__ void adam_block(const TList& list, const AdamCoef& c,
     // unaligned arrays (a gradient view at an odd offset of the flat buffer): lane-consecutive elements
     for (int64_t j = i0 + threadIdx.x; j < i0 + kAdamBlock && j < T.n; j += 256) {
       float p = T.p[j], m = T.m[j], v = T.v[j];
-      adam_elem(c, p, T.g[j], m, v);
+      adam_elem<EW>(c, p, T.g[j], m, v);
       T.m[j] = m;
       T.v[j] = v;
       T.p[j] = p;
@@ -1700,7 +1687,7 @@ __device__ __forceinline__ void adam_block(const TList& list, const AdamCoef& c,
       for (int k = 0; k < 4; ++k) {
         if (i + k >= T.n) break;
         float pp = T.p[i + k], mm = T.m[i + k], vv = T.v[i + k];
-        adam_elem(c, pp, T.g[i + k], mm, vv);
+        adam_elem<EW>(c, pp, T.g[i + k], mm, vv);
         T.m[i + k] = mm;
         T.v[i + k] = vv;
         T.p[i + k] = pp;
@@ -1711,19 +1698,10 @@ __device__ __forceinline__ void adam_block(const TList& list, const AdamCoef& c,
 
 __global__ void __launch_bounds__(256) adam_kernel(const AdamList list, float step_size, float omb1, float b2,
                                                    float omb2, float eps, float wd, float bc2_sqrt) {
-  adam_block(list, AdamCoef{step_size, omb1, b2, omb2, eps, wd, bc2_sqrt}, blockIdx.x);
+  adam_block<kAdamFuseV>(list, AdamCoef{step_size, omb1, b2, omb2, eps, wd, bc2_sqrt}, blockIdx.x);
 }
 
-// Graph-replayable Adam: every workgroup derives the step's scalars from the device counter + 1 (in double, as
-// torch does from Python floats, then f32) -- no separate prep launch; in the step's last launch the last workgroup
-// to finish (a ticket counter) advances the counter, after every workgroup of the step has read it.
-__device__ __forceinline__ AdamCoef adam_coef(int64_t step, const AdamHyper& h) {
-  const double bc1 = 1.0 - pow(h.b1, (double)step);
-  const double bc2 = 1.0 - pow(h.b2, (double)step);
-  return AdamCoef{(float)(h.lr / bc1), (float)(1.0 - h.b1), (float)h.b2, (float)(1.0 - h.b2), (float)h.eps,
-                  (float)h.wd, (float)sqrt(bc2)};
-}
-
+// Graph-replayable Adam (adam_coef, dfwfm_adam.h)
 // (a bounded grid walking the 1024-element blocks: one ticket atomic per workgroup, a few thousand at most -- one
 // per block serialised on the counter's address)
 template <typename TList>
@@ -1736,19 +1714,8 @@ __device__ __forceinline__ void adam_dev_part(const TList& list, AdamDevState* _
     sc = adam_coef(s_step, h);
   }
   __syncthreads();
-  for (int b = wg; b < nblocks; b += nwg) adam_block(list, sc, b);
-  if (bump && threadIdx.x == 0 && atomicAdd(&st->ticket, 1) == nwg - 1) {
-    const AdamCoef c = sc;
-    st->step_size = c.step_size;
-    st->omb1 = c.omb1;
-    st->b2 = c.b2;
-    st->omb2 = c.omb2;
-    st->eps = c.eps;
-    st->wd = c.wd;
-    st->bc2_sqrt = c.bc2_sqrt;
-    st->ticket = 0;
-    st->step = s_step;
-  }
+  for (int b = wg; b < nblocks; b += nwg) adam_block<kAdamFuseG>(list, sc, b);
+  if (bump && threadIdx.x == 0 && atomicAdd(&st->ticket, 1) == nwg - 1) adam_advance(st, sc, s_step);
 }
 
 __global__ void __launch_bounds__(256) adam_dev_kernel(const AdamList list, AdamDevState* __restrict__ st,

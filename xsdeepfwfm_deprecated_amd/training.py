@@ -179,14 +179,24 @@ class FusedTrainStep:
     e.g. a loader double-buffering into fixed tensors) are read in place -- one captured graph set per buffer
     set (at most ``max_graph_sets``, least recently used dropped) -- instead of being copied into the step's
     own input buffers first (three copy launches per step).  step_many (several steps per graph) needs it: its
-    graphs read their batches in place and live in a cache of their own (``max_many_sets``)."""
+    graphs read their batches in place and live in a cache of their own (``max_many_sets``).
+
+    lazy_table_adam: the categorical tables' Adam updates only the rows the step's batch touched (include/
+    dfwfm_lazy_adam.h: torch.optim.SparseAdam / LazyAdam semantics -- an untouched row gets no moment decay and no
+    L2 that step, which is NOT the reference's dense Adam), and the tables' region of the gradient buffer is no longer
+    filled every step: the lazy call zeroes the rows it updates, which are the rows the scatter wrote.  Everything
+    that is not a categorical table stays on the dense Adam.  One process only."""
 
     def __init__(self, model, batch_size, lr=1e-3, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8,
                  use_graph=True, dist=None, sparse_exchange=True, resident_inputs=False, max_graph_sets=8,
-                 max_many_sets=2, deterministic=None):
+                 max_many_sets=2, deterministic=None, lazy_table_adam=False):
         dev = model._device()
         if dev.type != "cuda":
             raise _lib.DfwfmError("FusedTrainStep runs only on a HIP device")
+        if lazy_table_adam and dist is not None:
+            # the touched set of a data-parallel step is the union of every rank's exchanged lists (DESIGN.md section 9)
+            raise NotImplementedError("lazy_table_adam under data parallelism: the touched rows are the union of the "
+                                      "ranks' exchanged lists, which the lazy step does not read yet")
         self.model, self.dev = model, dev
         self.B = int(batch_size)
         self.lr, self.wd, self.betas, self.eps = float(lr), float(weight_decay), tuple(betas), float(eps)
@@ -258,6 +268,12 @@ class FusedTrainStep:
         # one process: Adam as two launches, the categorical tables (state_t) and the rest (state), on every path
         # (eager, graph, step_many), so the two counters always hold the same step
         self.split_adam = dist is None and 0 < self.n_cat < len(params)
+        # lazy_table_adam: the tables' Adam over the batch's touched rows only (no categorical table: nothing to do)
+        self.lazy = bool(lazy_table_adam) and self.n_cat > 0
+        if self.lazy:
+            if not self.split_adam:
+                raise NotImplementedError("lazy_table_adam: a model whose only trainable parameters are tables")
+            self._setup_lazy(fields, params[:self.n_cat], views)
         ptr = lambda t: None if t is None else views[id(t)].data_ptr()  # noqa: E731
         # sparse exchange: the backward scatters the categorical tables' gradients into a rank-local buffer (same
         # offsets as in self.grad, whose categorical region the lists fill); dfwfm_sparse_grads_local turns its
@@ -359,6 +375,48 @@ class FusedTrainStep:
                                                            ctypes.c_void_p(rb + f["o_cnt"]), f["cap"], st),
                            "dfwfm_sparse_grads_apply")
 
+    def _setup_lazy(self, fields, tables, views):
+        """The table descriptors of dfwfm_lazy_adam_step_dev: every categorical table with its xi column, its key
+        range (the forward's: a QR field accepts every key whose quotient row exists) and its slice of the stamps."""
+        desc = {}
+        for f in range(self.model.num, self.model.field_size):
+            e2, e2r, e1, e1r = fields[f]
+            ref = e2 if e2 is not None else e1
+            qr = (e2r if e2 is not None else e1r) is not None
+            bag = (self.model.fm_2nd_embeddings if e2 is not None else self.model.fm_1st_embeddings)[f]
+            c = int(bag.num_collisions) if qr else 0
+            keys = int(ref.shape[0]) * c if qr else int(ref.shape[0])
+            for q, r in ((e2, e2r), (e1, e1r)):
+                if q is not None:
+                    desc[id(q)] = (f - self.model.num, keys, _lib.LAZY_QUOTIENT if qr else _lib.LAZY_PLAIN, c)
+                if r is not None:
+                    desc[id(r)] = (f - self.model.num, keys, _lib.LAZY_REMAINDER, c)
+        self.lazy_stamp = torch.zeros(sum(int(p.shape[0]) for p in tables), dtype=torch.int32, device=self.dev)
+        self.lazy_tables = (_lib.dfwfm_lazy_adam_table * len(tables))()
+        row0 = 0
+        for i, p in enumerate(tables):
+            col, keys, kind, c = desc[id(p)]
+            rows, width = int(p.shape[0]), p.numel() // int(p.shape[0])
+            g = views[id(p)]
+            off = (g.data_ptr() - self.grad.data_ptr()) // 4
+            self.lazy_tables[i] = _lib.dfwfm_lazy_adam_table(
+                p.data_ptr(), g.data_ptr(), self.exp_avg[off:].data_ptr(), self.exp_avg_sq[off:].data_ptr(),
+                self.lazy_stamp[row0:].data_ptr(), rows, keys, c, width, col, kind, 0)
+            row0 += rows
+
+    def _adam_tables(self, n):
+        """The categorical tables' Adam on state_t: every row (dense), or under lazy_table_adam the rows that the
+        first n samples of the step's input buffer touch."""
+        if not self.lazy:
+            self._adam_range(self.adam, self.n_cat, self.state_t)
+            return
+        b1, b2 = self.betas
+        xi = self._in[0]
+        _lib.check(self.L.dfwfm_lazy_adam_step_dev(self.lazy_tables, self.n_cat, ctypes.c_void_p(xi.data_ptr()),
+                                                   xi.stride(0), n, self.lr, b1, b2, self.eps, self.wd,
+                                                   ctypes.c_void_p(self.state_t.data_ptr()), self._stream()),
+                   "dfwfm_lazy_adam_step_dev")
+
     def close(self):
         """Detach the engine from this step's device counter (the engine outlives the trainer: a later
         train forward must not read the freed counter).  Idempotent; also run by __del__."""
@@ -387,9 +445,11 @@ class FusedTrainStep:
     def _part1(self, n, denom, phases=None):
         L, st, h = self.L, self._stream(), self.eng.handle
         self.eng.set_deterministic(self.deterministic)  # read when the backward launches are enqueued / captured
-        # the dense weights re-packed and the gradient buffer zeroed in one launch
-        _lib.check(L.dfwfm_model_set_dense_zero(h, *self.dense_args, ctypes.c_void_p(self.grad.data_ptr()),
-                                                self.grad.numel(), st), "dfwfm_model_set_dense_zero")
+        # the dense weights re-packed and the gradient buffer zeroed in one launch (lazy_table_adam: all but the
+        # categorical tables' region, which the lazy step leaves zero)
+        z0 = self.n_tables if self.lazy else 0
+        _lib.check(L.dfwfm_model_set_dense_zero(h, *self.dense_args, ctypes.c_void_p(self.grad[z0:].data_ptr()),
+                                                self.grad.numel() - z0, st), "dfwfm_model_set_dense_zero")
         xi, xv, y = self._in
         _lib.check(L.dfwfm_train_forward(h, ctypes.c_void_p(xi.data_ptr()), xi.stride(0),
                                          ctypes.c_void_p(xv.data_ptr()), xv.stride(0), n,
@@ -429,7 +489,7 @@ class FusedTrainStep:
         with torch.cuda.stream(s1):
             self._backward_phase(_lib.BWD_SCATTER)
             if self.split_adam:  # the tables' Adam right behind their scatter, beside the GEMM
-                self._adam_range(self.adam, self.n_cat, self.state_t)
+                self._adam_tables(self.B)
         self._backward_phase(_lib.BWD_REDUCE | _lib.BWD_MLP_WEIGHTS)
         if self.split_adam:
             self._adam_range(self.adam_rest, self.n_adam - self.n_cat, self.state)
@@ -460,9 +520,9 @@ class FusedTrainStep:
                                                   self.wd, ctypes.c_void_p(self.state_b.data_ptr()), self._stream()),
                        "dfwfm_adam_step_dev")
 
-    def _part2(self):
+    def _part2(self, n=None):
         if self.split_adam:  # the tables (state_t) then the rest (state): both counters bumped every step
-            self._adam_range(self.adam, self.n_cat, self.state_t)
+            self._adam_tables(self.B if n is None else n)
             self._adam_range(self.adam_rest, self.n_adam - self.n_cat, self.state)
             return
         if self.dist is None:
@@ -696,7 +756,7 @@ class FusedTrainStep:
             self._in = inputs
             self._part1(n, denom)
             self._exchange(self._part1b if self._bucketed() else (lambda: None), self._apply_sparse)
-            self._part2()
+            self._part2(n)
         self.steps += 1
         self.eng._dense_key = None  # weights changed behind torch's version counters: re-pack on next use
         self.eng._packed_key = None  # (the tables' serving copy too)
@@ -957,8 +1017,13 @@ def fit(model, Xi_train, Xv_train, y_train, Xi_valid=None, Xv_valid=None, y_vali
         device.type == "cuda"  # on the CPU: the host kernels through autograd + torch.optim.Adam
     bs = model.batch_size
     gbs = bs * world
+    lazy = bool(getattr(model, "lazy_table_adam", False))
+    if lazy and not fused:
+        # never train silently with another optimizer's semantics: the lazy update exists on the fused step only
+        raise ValueError("lazy_table_adam needs the fused training step: a module on a HIP device, "
+                         "optimizer_type='adam', no teacher model and fused_fit on")
     trainer = FusedTrainStep(model, bs, lr=model.learning_rate, weight_decay=model.weight_decay,
-                             dist=dist) if fused else None
+                             dist=dist, lazy_table_adam=lazy) if fused else None
     try:
         return _fit_loop(model, trainer, dist, rank, world, Xi_train, Xv_train, y_train, x_size, ncat, is_valid,
                          Xi_valid if is_valid else None, Xv_valid if is_valid else None,
