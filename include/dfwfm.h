@@ -376,7 +376,10 @@ int dfwfm_prune_apply(float* values, int64_t numel, int32_t sym_f, const double*
  * From logits z and labels y (device, n each): pred = sigmoid(z) in f32; writes 8 doubles to out_dev:
  * {roc_auc_score(y, pred), auc(precision_recall_curve), log_loss, RCE, CTR, positives, n, distinct
  * predictions}, the sklearn 1.7 definitions (ties grouped, [1-p, p] renormalised and clipped to the
- * float64 eps).  AUC is NaN when only one class is present (sklearn raises). */
+ * float64 eps).  AUC is NaN when only one class is present (sklearn raises).  Without positives the PR value is
+ * 0.5: sklearn's curve there, recall 1 at every threshold, then (0, 1); without negatives it is 1.  A NaN logit makes
+ * AUC, PR AUC, log_loss and RCE NaN (sklearn raises ValueError; a diverged model gets no believable evaluation);
+ * CTR, positives and n do not depend on the logits. */
 int64_t dfwfm_metrics_workspace_bytes(int64_t n);
 int dfwfm_eval_metrics(const float* logits, const float* labels, int64_t n, double* out_dev, void* workspace,
                        int64_t workspace_bytes, void* stream);

@@ -10,10 +10,13 @@
 //   ROC AUC   = sum_g (n_g - p_g) * (P_above + p_g / 2) / (P * N)     (Mann-Whitney with ties = the
 //               trapezoid under sklearn's ROC, which has one point per distinct threshold)
 //   PR AUC    = trapezoid over sklearn's PR curve: (recall 0, precision 1), then one point per
-//               distinct threshold from the highest: recall = TP/P, precision = TP/(TP+FP)
+//               distinct threshold from the highest: recall = TP/P, precision = TP/(TP+FP).  Without positives
+//               (P = 0) sklearn sets recall to 1 at every threshold: the curve is (0, 1) -> (1, 0) and the area 0.5
 //   log_loss  = mean of -[y log q + (1-y) log(1-q)], q = [1-p, p] renormalised, clipped to
 //               [eps, 1-eps] (double eps), as sklearn 1.7
 //   RCE       = (1 - log_loss / log_loss(constant CTR)) * 100
+// A NaN logit makes AUC, PR AUC, log_loss and RCE NaN (sklearn raises ValueError on a NaN prediction; a kernel cannot,
+// and a diverged model must not get a believable evaluation); CTR, positives and n do not depend on the logits.
 // Every sum is formed per tile and the tiles are added in tile order (no float atomics): the same bits each run.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -32,6 +35,7 @@ constexpr int kTile = kT * kIPT;                // items per tile (workgroup)
 
 __device__ __forceinline__ double clipped_ll(double p, int y) {
   // sklearn: y_pred = [1 - p, p] / row sum, clipped; loss = -xlogy(onehot, y_pred)
+  if (p != p) return p;  // fmin / fmax would drop the NaN and return a finite loss
   double a = 1.0 - p, b = p;
   const double s = a + b;
   a /= s;
@@ -245,7 +249,8 @@ __global__ void __launch_bounds__(kT) metrics_groups_kernel(const int64_t* __res
       const double pa = (double)cpos[s], pe = e < n ? (double)cpos[e] : P;
       const double ng = (double)(e - s), pg = pe - pa, st = (double)s;
       roc += (ng - pg) * (pa + 0.5 * pg);
-      const double r0 = P > 0 ? pa / P : 1.0, r1 = P > 0 ? pe / P : 1.0;
+      // P == 0: recall 1 at every threshold after the curve's first point (recall 0, precision 1)
+      const double r0 = P > 0 ? pa / P : (g == 0 ? 0.0 : 1.0), r1 = P > 0 ? pe / P : 1.0;
       const double p0 = g == 0 ? 1.0 : pa / st;
       const double p1 = pe / (st + ng);
       pr += (r1 - r0) * (p0 + p1) * 0.5;
@@ -292,8 +297,9 @@ __global__ void __launch_bounds__(kT) metrics_final_kernel(const double* __restr
   if (P > 0) straw += P * clipped_ll(c, 1);
   if (N > 0) straw += N * clipped_ll(c, 0);
   straw /= (double)n;
-  out[0] = (P > 0 && N > 0) ? t[2] / (P * N) : nan("");
-  out[1] = t[3];
+  const bool poisoned = ll != ll;  // a NaN logit: its rank means nothing either
+  out[0] = (P > 0 && N > 0 && !poisoned) ? t[2] / (P * N) : nan("");
+  out[1] = poisoned ? ll : t[3];
   out[2] = ll;
   out[3] = (1.0 - ll / straw) * 100.0;
   out[4] = c;
@@ -311,7 +317,7 @@ struct MetricsWs {
   int64_t* offs;       // their exclusive scan
   int64_t* cpos;       // positives ranked above each position
   int64_t* gstart;     // start of each tie group
-  int64_t* tsum;       // scan tile sums (the largest scan: 256 x tiles items)
+  int64_t* tsum;       // scan tile sums (the scans run over n items and over 256 x tiles items)
   int64_t* scal;       // [0] scan total (scratch), [1] positives, [2] groups
   double* prep;        // per tile: log-loss, positives
   double* grp;         // per tile of groups: roc, pr
@@ -338,7 +344,7 @@ MetricsWs carve(void* base, int64_t n) {
   w.offs = (int64_t*)take(256 * nt * 8);
   w.cpos = (int64_t*)take(n * 8);
   w.gstart = (int64_t*)take(n * 8);
-  w.tsum = (int64_t*)take(tiles_of(256 * nt) * 8);
+  w.tsum = (int64_t*)take((nt > tiles_of(256 * nt) ? nt : tiles_of(256 * nt)) * 8);
   w.scal = (int64_t*)take(4 * 8);
   w.prep = (double*)take(2 * nt * 8);
   w.grp = (double*)take(2 * nt * 8);
