@@ -1,0 +1,151 @@
+"""CPU: the numpy statement of the int8 deep tower's numeric contract (tests/int8_emul.py, include/dfwfm_int8.h) -- its
+quantizers at their edges, its exact case exact and not degenerate, its error against the float64 oracle, and the
+tolerance conditions of the GPU tests between the two epilogue roundings of the reference itself."""
+import numpy as np
+import pytest
+
+import bf16_emul
+import int8_emul
+from conftest import load_golden
+from oracle import dfwfm_oracle
+from xsdeepfwfm_deprecated_amd import _lib
+
+f32 = np.float32
+
+
+@pytest.fixture(autouse=True)
+def contract_has_a_path():
+    """The emulation states the contract of a path the library has (include/dfwfm_int8.h); without it these tests
+    would describe nothing."""
+    assert "dfwfm_int8_forward" in _lib.INT8_SIGNATURES
+
+
+def _reference_alone(cfg, params, xi, xv, r, e, eb, what):
+    """The emulation with the other epilogue rounding (a f32 multiply, then a f32 add) stays within the GPU tests'
+    conditions of the emulation proper; fmt is finite, below 1e-2 and above the bf16 format's."""
+    o = int8_emul.forward(cfg, params, xi, xv, fma=False)
+    c = int8_emul.conditions(o, e, r)
+    fmt_bf16 = int8_emul.conditions(eb, eb, r)["fmt"]
+    print("fmt", what, dict(int8=c["fmt"], bf16=fmt_bf16, mul_add_close=c["close"], mul_add_worst=c["worst_ge"]))
+    assert np.isfinite(c["fmt"]) and c["fmt"] < 1e-2
+    assert c["fmt"] > fmt_bf16
+    assert c["close"] >= 0.99, (what, c)
+    assert c["worst_ge"] <= max(1e-5, c["fmt"]), (what, c)
+    assert c["worst_gr"] <= 2 * c["fmt"], (what, c)
+
+
+@pytest.mark.parametrize("name", int8_emul.DEEP_GOLDENS)
+def test_gpu_conditions_hold_for_the_reference_alone_goldens(name):
+    cfg, params, xi, xv, y, r, e = int8_emul.golden_case(name)
+    _reference_alone(cfg, params, xi, xv, r, e, bf16_emul.golden_case(name)[6], name)
+
+
+@pytest.mark.parametrize("i", range(len(int8_emul.SWEEP)))
+def test_gpu_conditions_hold_for_the_reference_alone_sweep(i):
+    cfg, params, xi, xv, r, e = int8_emul.sweep_ref(i)
+    _reference_alone(cfg, params, xi, xv, r, e, bf16_emul.sweep_ref(i)[5], int8_emul.SWEEP[i])
+
+
+def test_sweep_split_into_supported_and_unsupported():
+    assert [int8_emul.SWEEP[i][:3] for i in int8_emul.SWEEP_SUPPORTED] == [(39, 13, 10)] * 4
+    assert len(int8_emul.SWEEP_UNSUPPORTED) == len(int8_emul.SWEEP) - 4
+
+
+def test_tiny_golden_auc():
+    from sklearn.metrics import roc_auc_score
+    cfg, params, xi, xv, y, r, e = int8_emul.golden_case("tiny_deepfwfm_lw")
+    auc_ref = float(load_golden("tiny_deepfwfm_lw")[7])
+    assert len(y) == 2000
+    auc = roc_auc_score(y, dfwfm_oracle.sigmoid(e))
+    print("tiny_deepfwfm_lw AUC", auc, "auc_ref", auc_ref)
+    assert abs(auc - auc_ref) <= 1e-4
+
+
+# ---- the quantizers at their edges ------------------------------------------------------------------------------------
+def test_weight_quantizer_edges():
+    W = np.array([[0, 0, 0, 0], [1, -0.5, 0.25, 0], [-3, 3, 1.5, 1e-3], [127, 63.5, 64.5, -62.5]], dtype=f32)
+    q, sw = int8_emul.quantize_weights(W)
+    assert sw[0] == 1 and (q[0] == 0).all()  # an all-zero row: scale 1 and zeros
+    assert sw[1] == f32(1) / f32(127) and q[1].tolist() == [127, -64, 32, 0]  # 63.5 and 31.75 (ties to even, nearest)
+    assert q[2].tolist()[:2] == [-127, 127] and np.abs(q).max() == 127
+    assert sw[3] == 1 and q[3].tolist() == [127, 64, 64, -62]  # exact ties round to even
+
+
+def test_row_quantizer_edges():
+    x = np.zeros((5, 8), dtype=f32)
+    x[1] = [127, 63.5, 64.5, -63.5, -0.5, 0.5, 1.5, -127]  # inv = 1: exact ties, to even
+    x[2] = [254, 255, -1000, 1, 0, 0, 0, 0]
+    x[3, 2] = np.nan
+    x[4] = [1, 2, np.inf, 3, 0, 0, 0, 0]
+    q, sx, inv = int8_emul.quantize_rows(x)
+    assert inv[0] == 0 and sx[0] == 0 and (q[0] == 0).all()  # a zero row
+    assert inv[1] == 1 and sx[1] == 1 and q[1].tolist() == [127, 64, 64, -64, 0, 0, 2, -127]
+    assert q[2].min() == -127 and np.abs(q).max() == 127  # the clamp (the max itself maps to +-127)
+    assert np.isnan(sx[3]) and (q[3] == 0).all()
+    assert np.isinf(sx[4]) and inv[4] == 0 and (q[4] == 0).all()
+    # the clamp proper: a product past 127 by rounding of inv stays 127
+    big = np.array([[3.0000002, -3.0000002, 1, 0]], dtype=f32)
+    assert np.abs(int8_emul.quantize_rows(big)[0]).max() == 127
+
+
+def test_zero_activation_row_gives_relu_of_the_bias():
+    cfg = dict(h_depth=1)
+    rs = np.random.RandomState(3)
+    params = {"net_1_linear_1.weight": rs.standard_normal((16, 20)).astype(f32),
+              "net_1_linear_1.bias": rs.standard_normal(16).astype(f32)}
+    x = rs.standard_normal((3, 20)).astype(f32)
+    x[1] = 0
+    h = int8_emul.tower(cfg, params, x)
+    assert np.array_equal(h[1], np.maximum(params["net_1_linear_1.bias"], 0))
+    assert not np.array_equal(h[0], h[1])
+
+
+@pytest.mark.parametrize("bad", [np.nan, np.inf, -np.inf])
+def test_nan_or_inf_in_a_row_makes_that_row_nan_and_no_other(bad):
+    cfg, params, xi, xv = int8_emul.sweep_case(*int8_emul.SWEEP[7], rows=8)
+    xv = xv.copy()
+    base = int8_emul.forward(cfg, params, xi, xv)
+    xv[5, 2] = bad
+    got = int8_emul.forward(cfg, params, xi, xv)
+    assert np.isnan(got[5])
+    keep = np.arange(8) != 5
+    assert np.array_equal(got[keep], base[keep]) and np.isfinite(base).all()
+
+
+# ---- the exact case ---------------------------------------------------------------------------------------------------
+def test_exact_case_is_exact():
+    cfg, params, xi, xv = int8_emul.exact_case()
+    assert xi.shape[0] == 96 and cfg["h_depth"] == 2 and cfg["deep_nodes"] == 400 and cfg["field_size"] == 39
+    ref = dfwfm_oracle.forward(cfg, params, xi, xv)
+    assert np.array_equal(ref.astype(f32).astype(np.float64), ref)  # the oracle's logits are float32 values
+    for fma in (True, False):
+        assert np.array_equal(int8_emul.forward(cfg, params, xi, xv, fma=fma).astype(f32), ref.astype(f32))
+    # every hidden value of the contract is the oracle's
+    _, parts = dfwfm_oracle.forward(cfg, params, xi, xv, return_parts=True)
+    E = parts["E"].reshape(96, -1)
+    _, hidden = int8_emul.tower(cfg, params, E.astype(f32), return_hidden=True)
+    h = E
+    for l in (1, 2):
+        h = np.maximum(h @ params[f"net_1_linear_{l}.weight"].T.astype(np.float64)
+                       + params[f"net_1_linear_{l}.bias"].astype(np.float64), 0.0)
+        assert np.array_equal(hidden[l - 1].astype(np.float64), h)
+        if l == 1:
+            assert h.max() == 31.75 and np.array_equal(h * 4, np.round(h * 4))
+
+
+def test_exact_case_is_not_degenerate():
+    cfg, params, xi, xv = int8_emul.exact_case()
+    total, parts = dfwfm_oracle.forward(cfg, params, xi, xv, return_parts=True)
+    assert (parts["deep"] != 0).mean() >= 0.5
+    assert len(np.unique(total.astype(f32))) >= 0.9 * len(total)
+    # the placement the case promises: the first and last real k and every 64-wide K step carry useful weights
+    for l in (1, 2):
+        W = params[f"net_1_linear_{l}.weight"].copy()
+        W[:, 1] = 0  # the scale entries, on the always-zero column
+        used = np.abs(W).sum(0) > 0
+        assert used[0] and used[-1]
+        assert all(used[c:c + 64].any() for c in range(0, W.shape[1], 64))
+    # a wrong layer-1 or layer-2 sum moves the logits: the hidden layers reach the output
+    p2 = dict(params)
+    p2["net_1_linear_2.weight"] = params["net_1_linear_2.weight"] * f32(0.5)
+    assert (dfwfm_oracle.forward(cfg, p2, xi, xv) != total).mean() >= 0.5

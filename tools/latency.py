@@ -7,7 +7,7 @@ with HIP events around it (device time) and by the host clock around launch + sy
 batch's forward is also replayed from a one-forward hipGraph (launch overhead of a serving loop that captures).
 Prints one JSON line.
 
-  python tools/latency.py [--calls 1000] [--batches 1,16,64,256,1024,4096,8192] [--small] [--bf16] [--bf16-fused]
+  python tools/latency.py [--calls 1000] [--batches 1,16,64,256,1024,4096,8192] [--small] [--bf16] [--bf16-fused] [--int8]
 
 --small: the small-batch serving forward (eng.forward_small, include/dfwfm_serve.h) measured beside eng.forward at
 every batch, same figures, under models["deepfwfm_small"] (the batch where it stops winning is the value to give
@@ -25,6 +25,11 @@ through eng.forward_bf16_batches: forward_bf16_batches_4096_us and forward_bf16_
 (81920 rows: 20 resident batches of 4096, beside forward_batches_4096_us_per_batch of the f32 row).  The same calls
 with the numerical fields folded into layer 1 (eng.sync_bf16_fold, include/dfwfm_bf16_fold.h) are measured right
 behind the unfolded ones at every batch, same figures, under models["deepfwfm_bf16_fused_fold"].
+
+--int8: the one-launch forward with an int8 deep tower (eng.forward_int8, include/dfwfm_int8.h) beside eng.forward (and
+eng.forward_bf16_fused with --bf16-fused) in the same process at every batch, same figures, under
+models["deepfwfm_int8"]; and the batch-set leg through eng.forward_int8_batches: forward_int8_batches_4096_us and
+forward_int8_batches_4096_us_per_batch in that row.  DFWFM_DIAG int8rows=16|32 forces its row tile (A/B).
 """
 import argparse
 import json
@@ -126,6 +131,8 @@ def main():
     ap.add_argument("--bf16", action="store_true", help="also measure eng.forward_bf16 (deep model)")
     ap.add_argument("--bf16-fused", action="store_true",
                     help="also measure eng.forward_bf16_fused and eng.forward_bf16_batches (deep model; implies --bf16)")
+    ap.add_argument("--int8", action="store_true",
+                    help="also measure eng.forward_int8 and eng.forward_int8_batches (deep model)")
     a = ap.parse_args()
     a.bf16 = a.bf16 or a.bf16_fused
     batches = [int(x) for x in a.batches.split(",")]
@@ -139,11 +146,13 @@ def main():
                    "(data/results/criteo.md:5)", "calls": a.calls, "models": {}}
     for name, deep in (("deepfwfm", 1), ("fwfm", 0)):
         m, sizes = build(deep, dev)
-        rows, small, bf16, fused, folded = {}, {}, {}, {}, {}
+        rows, small, bf16, fused, folded, int8 = {}, {}, {}, {}, {}, {}
         with torch.no_grad():
             eng = m._sync_engine(dev)
             if a.bf16 and deep:
                 eng.sync_bf16(True)
+            if a.int8 and deep:
+                eng.sync_int8(True)
             num_tabs = [m.fm_2nd_embeddings[f].weight.detach() for f in range(13)]
 
             def fold(on):  # the folded layer 1 of the fused bf16 forward on / off (one pack launch)
@@ -171,10 +180,16 @@ def main():
                     fold(True)
                     stats(eng.forward_bf16_fused, folded, b, xi, xv, out, calls)
                     fold(False)
-                if a.bf16 and deep and b >= 8192 and b % 4096 == 0:
+                if a.int8 and deep:
+                    stats(eng.forward_int8, int8, b, xi, xv, out, calls)
+                if (a.bf16 or a.int8) and deep and b >= 8192 and b % 4096 == 0:
                     t, nb = measure_batch_set(eng.forward_batches, xi, xv, out, dev)
                     rows[str(b)]["forward_batches_4096_us"] = round(t, 2)
                     rows[str(b)]["forward_batches_4096_us_per_batch"] = round(t / nb, 2)
+                    if a.int8:
+                        t, nb = measure_batch_set(eng.forward_int8_batches, xi, xv, out, dev)
+                        int8[str(b)]["forward_int8_batches_4096_us"] = round(t, 2)
+                        int8[str(b)]["forward_int8_batches_4096_us_per_batch"] = round(t / nb, 2)
                     if a.bf16_fused:
                         t, nb = measure_batch_set(eng.forward_bf16_batches, xi, xv, out, dev)
                         fused[str(b)]["forward_bf16_batches_4096_us"] = round(t, 2)
@@ -191,6 +206,8 @@ def main():
             res["models"][name + "_bf16_fused"] = fused
         if folded:
             res["models"][name + "_bf16_fused_fold"] = folded
+        if int8:
+            res["models"][name + "_int8"] = int8
         if small:
             res["models"][name + "_small"] = small
     print(json.dumps(res))

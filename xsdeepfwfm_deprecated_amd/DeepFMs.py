@@ -122,6 +122,9 @@ class DeepFMs(nn.Module):
         # -- bf16 MFMA with f32 accumulation (ForwardEngine.forward_bf16, include/dfwfm_bf16.h: the numeric contract),
         # the gather, first order and FwFM staying exact f32; it takes precedence over small_batch_rows.  Training is
         # f32 either way; a model without a deep tower ignores it
+        # "int8": the one-launch forward with the hidden layers on int8 MFMA, weights quantized per neuron, activations
+        # per row and layer (ForwardEngine.forward_int8, include/dfwfm_int8.h); bf16_fused /
+        # bf16_fold are ignored with it; an unsupported shape, an active FwFM pair list or a sparse tower raise DfwfmError
         self.mlp_dtype = "f32"
         # with mlp_dtype = "bf16": the bf16 forward as ONE launch with the E tile and the activations in LDS
         # (ForwardEngine.forward_bf16_fused, include/dfwfm_bf16_fused.h) instead of a launch per layer, and eval_by_batch's
@@ -300,6 +303,7 @@ class DeepFMs(nn.Module):
                 eng.sync_fold([second[f].weight.detach() for f in range(self.num)],
                               bool(getattr(self, "fold_numerical", True)))
             eng.small_rows = max(int(getattr(self, "small_batch_rows", 0)), 0) if self.use_deep else 0
+            eng.int8 = eng.sync_int8(self._mlp_int8()) if self.use_deep else False
             eng.bf16 = eng.sync_bf16(self._mlp_bf16()) if self.use_deep else False
             eng.bf16_fused = bool(eng.bf16 and getattr(self, "bf16_fused", False) and eng.bf16_fused_supported())
             if eng.bf16:  # the fused form's folded layer 1, rebuilt when W1, a numerical table or the bf16 copy changed
@@ -310,12 +314,22 @@ class DeepFMs(nn.Module):
     def _mlp_bf16(self) -> bool:
         """Whether mlp_dtype asks for the bf16 deep tower (validated here: at the next forward)."""
         dt = getattr(self, "mlp_dtype", "f32")
-        if dt not in ("f32", "bf16"):
+        if dt not in ("f32", "bf16", "int8"):
             raise ValueError(f"mlp_dtype must be 'f32' or 'bf16', got {dt!r}")
-        if not self.use_deep or dt == "f32":
+        if not self.use_deep or dt != "bf16":
             return False
         if self.sparse_mlp_max_density > 0:
             raise ValueError("mlp_dtype='bf16' and sparse_mlp_max_density > 0 are two deep towers: choose one")
+        return True
+
+    def _mlp_int8(self) -> bool:
+        """Whether mlp_dtype asks for the int8 deep tower (include/dfwfm_int8.h).  There is one int8 path and no
+        fallback: a sparse tower beside it is refused here, an unsupported shape or an active FwFM pair list by the
+        library (DfwfmError)."""
+        if not self.use_deep or getattr(self, "mlp_dtype", "f32") != "int8":
+            return False
+        if self.sparse_mlp_max_density > 0:
+            raise DfwfmError("mlp_dtype='int8' and sparse_mlp_max_density > 0 are two deep towers: choose one")
         return True
 
     def _sync_cpu_engine(self):
@@ -397,9 +411,16 @@ class DeepFMs(nn.Module):
         if device.type == "cpu" and self._mlp_bf16():
             raise DfwfmError("mlp_dtype='bf16' is the HIP-only bf16 MFMA path (include/dfwfm_bf16.h); "
                              "a CPU model runs mlp_dtype='f32'")
+        if device.type == "cpu" and getattr(self, "mlp_dtype", "f32") == "int8":
+            raise DfwfmError("mlp_dtype='int8' is the HIP-only int8 MFMA path (include/dfwfm_int8.h); "
+                             "a CPU model runs mlp_dtype='f32'")
         if device.type != "cpu":  # (the host kernel has no serving copy or pruned-layout variants)
             self._sync_inference(device)  # the tables' serving copy, re-packed after weight updates
-            if self.use_deep and not eng.bf16:
+            if self.use_deep and eng.int8:
+                # one int8 path: an active FwFM pair list makes dfwfm_int8_forward refuse rather than take another
+                if self.use_fwfm:
+                    eng.sync_pairs(self.fwfm_pair_max)
+            elif self.use_deep and not eng.bf16:
                 # magnitude-pruned hidden layers (fit(prune=1), reference :647-673) run as a sparse MLP when
                 # at most sparse_mlp_max_density of their weights are nonzero (checked once per weight update)
                 eng.sync_sparse(self.sparse_mlp_max_density)
@@ -498,13 +519,16 @@ class DeepFMs(nn.Module):
                 # the full batches as batch sets (dfwfm_forward_batches: up to 32 resident batches per launch, the
                 # same logits as one forward each); the sparse-MLP / pair-list variants keep one forward per batch
                 eng = self._sync_inference(dev)
-                alt = (eng.bf16 or eng.sync_sparse(self.sparse_mlp_max_density)) if self.use_deep else (
+                alt = (eng.int8 or eng.bf16 or eng.sync_sparse(self.sparse_mlp_max_density)) if self.use_deep else (
                     eng.sync_pairs(self.fwfm_pair_max) if self.use_fwfm else False)
                 # ... except the bf16 tower's fused form, which has batch sets of its own (dfwfm_bf16_fused_forward_batches)
                 fused = bool(self.use_deep and eng.bf16 and eng.bf16_fused)
-                if fused or not alt:
+                int8 = bool(self.use_deep and eng.int8)  # ... and the int8 tower (dfwfm_int8_forward_batches)
+                if fused or int8 or not alt:
                     nfull = x_size // bs
-                    call = eng.forward_bf16_batches if fused else eng.forward_batches
+                    call = eng.forward_batches
+                    if int8 or fused:
+                        call = eng.forward_int8_batches if int8 else eng.forward_bf16_batches
                     call([(Xi_d[i * bs:(i + 1) * bs], Xv_d[i * bs:(i + 1) * bs]) for i in range(nfull)],
                          [logits[i * bs:(i + 1) * bs] for i in range(nfull)])
                     for i in range(nfull):

@@ -24,7 +24,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libdfwfm.so")
 # A/B of build variants only (e.g. libdfwfm_ns4.so built with DFWFM_HIPCC_FLAGS=-DDFWFM_NSETS=4)
 LOAD_PATH = os.path.join(PKG_DIR, os.environ["DFWFM_LIB"]) if os.environ.get("DFWFM_LIB") else LIB_PATH
 SOURCES = ["dfwfm_kernels.hip", "dfwfm_fwd32.hip", "dfwfm_ftrain.hip", "dfwfm_train.hip", "dfwfm_prune.hip", "dfwfm_metrics.hip", "dfwfm_sparse.hip",
-           "dfwfm_spmlp.hip", "dfwfm_serve.hip", "dfwfm_bf16.hip", "dfwfm_bf16_fused.hip", "dfwfm_lazy_adam.hip",
+           "dfwfm_spmlp.hip", "dfwfm_serve.hip", "dfwfm_bf16.hip", "dfwfm_bf16_fused.hip", "dfwfm_int8.hip", "dfwfm_lazy_adam.hip",
            "dfwfm_capi.hip"]
 # the forward / backward kernel templates are instantiated once per embedding size, each size in its own
 # translation unit (-DDFWFM_KD=<D>) so they compile in parallel; the plain object holds everything else
@@ -41,7 +41,7 @@ def _units():
 HEADERS = ["dfwfm_internal.h", "dfwfm_device.h", "dfwfm_adam.h", os.path.join("..", "..", "include", "dfwfm.h"),
            os.path.join("..", "..", "include", "dfwfm_serve.h"), os.path.join("..", "..", "include", "dfwfm_bf16.h"),
            os.path.join("..", "..", "include", "dfwfm_bf16_fused.h"), os.path.join("..", "..", "include", "dfwfm_fold.h"),
-           os.path.join("..", "..", "include", "dfwfm_bf16_fold.h"),
+           os.path.join("..", "..", "include", "dfwfm_bf16_fold.h"), os.path.join("..", "..", "include", "dfwfm_int8.h"),
            os.path.join("..", "..", "include", "dfwfm_lazy_adam.h")]
 ARCH = os.environ.get("DFWFM_OFFLOAD_ARCH", "gfx950")
 CPU_PATH = os.path.join(PKG_DIR, "libdfwfm_cpu.so")
@@ -204,6 +204,17 @@ FOLD_SIGNATURES = {
 BF16_FOLD_SIGNATURES = {
     "dfwfm_bf16_fold_abi_version": (ctypes.c_int, []),
     "dfwfm_model_fold_bf16": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), _P]),
+}
+
+# the one-launch forward with an int8 deep tower, with batch sets (include/dfwfm_int8.h): same library, its own header
+# and ABI version
+INT8_SIGNATURES = {
+    "dfwfm_int8_abi_version": (ctypes.c_int, []),
+    "dfwfm_model_pack_int8": (ctypes.c_int, [_P, _P]),
+    "dfwfm_int8_supported": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int)]),
+    "dfwfm_int8_forward": (ctypes.c_int, [_P, _P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int64, _P, _P]),
+    "dfwfm_int8_forward_batches": (ctypes.c_int, [_P, ctypes.c_int32, _P, ctypes.c_int64, _P, ctypes.c_int64,
+                                                  ctypes.c_int64, _P, _P]),
 }
 
 # the row-lazy Adam step of the categorical tables (include/dfwfm_lazy_adam.h): same library, its own header and ABI
@@ -444,6 +455,12 @@ def lib():
             fn.argtypes = args
         if L.dfwfm_lazy_adam_abi_version() != 1:
             raise DfwfmError("libdfwfm lazy Adam ABI mismatch")
+        for name, (res, args) in INT8_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        if L.dfwfm_int8_abi_version() != 1:
+            raise DfwfmError("libdfwfm int8 ABI mismatch")
         _lib = L
     return _lib
 

@@ -66,9 +66,9 @@ def get_parser():
     a("-twitter_category", default="like", type=str, choices=["reply", "retweet", "retweet_comment", "like"])
     a("-time_on_cuda", default=0, type=int)
     a("-data_root", default=".", type=str, help="directory holding data/ (this engine's addition)")
-    a("-mlp_dtype", default="f32", type=str, choices=["f32", "bf16"],
-      help="deep tower of the inference forward: f32, or bf16 MFMA with f32 accumulation (HIP only; this "
-           "engine's addition, DeepFMs.mlp_dtype)")
+    a("-mlp_dtype", default="f32", type=str, choices=["f32", "bf16", "int8"],
+      help="deep tower of the inference forward: f32, bf16 MFMA with f32 accumulation, or int8 MFMA with per-neuron "
+           "weight and per-row activation scales (HIP only; this engine's addition, DeepFMs.mlp_dtype)")
     a("-bf16_fused", default=0, type=int, choices=[0, 1],
       help="with -mlp_dtype bf16: the bf16 forward as one launch, and batch sets of it in the evaluation "
            "(DeepFMs.bf16_fused; the same logits; an unsupported shape keeps the per-layer path)")

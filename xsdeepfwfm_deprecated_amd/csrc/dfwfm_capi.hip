@@ -16,6 +16,7 @@
 #include "../../include/dfwfm_bf16.h"
 #include "../../include/dfwfm_bf16_fold.h"
 #include "../../include/dfwfm_bf16_fused.h"
+#include "../../include/dfwfm_int8.h"
 #include "../../include/dfwfm_fold.h"
 #include "../../include/dfwfm_lazy_adam.h"
 
@@ -71,6 +72,11 @@ struct dfwfm_model {
   // dfwfm_model_fold_bf16 (include/dfwfm_bf16_fold.h): layer 1's folded bf16 fragments [NT][bf16_fold_steps][64][8]
   uint16_t* d_wbf16f;
   bool bf16fold_on;   // they match the parameters, the tables and the copy (cleared by set_dense / set_tables / pack_bf16)
+  // dfwfm_model_pack_int8 (include/dfwfm_int8.h): the int8 weights in MFMA operand order; sw [H][NT*16] then the
+  // biases [H][NT*16]
+  int8_t* d_wi8;
+  float* d_i8s;
+  bool int8_on;       // the pack matches the dense parameters set (cleared by set_dense)
   // dfwfm_model_fold_numerical (include/dfwfm_fold.h): layer 1's folded forward fragments [NT][foldNC][64]
   int foldNC;          // chunks of the folded pack (0: this model never folds)
   int foldSX, foldW0;  // the folded tile's row stride and valid columns past the E tile's start
@@ -159,7 +165,7 @@ void free_model(dfwfm_model* m) {
   void* ptrs[] = {m->d_fields, m->d_upack, m->d_err,     m->d_wpack, m->d_mlp_b,   m->d_fc,  m->d_fwlw,
                   m->d_lw,     m->d_bias,  m->d_stamps,  m->d_wtpack, m->d_rsk,   m->d_ws,
                   m->d_ell,    m->d_cnt,   m->d_spstat, m->d_pairs, m->d_pkrows, m->d_pk,
-                  m->d_wbf16,  m->d_wbf16f};
+                  m->d_wbf16,  m->d_wbf16f, m->d_wi8,    m->d_i8s};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   delete m;
@@ -492,6 +498,7 @@ static int set_dense_impl(dfwfm_model* m, const float* field_cov, const float* f
   m->bf16_on = false;  // and the bf16 copy until dfwfm_model_pack_bf16
   m->fold_on = false;  // and the folded layer 1 until dfwfm_model_fold_numerical
   m->bf16fold_on = false;  // ... of the bf16 tower until dfwfm_model_fold_bf16
+  m->int8_on = false;  // and the int8 pack until dfwfm_model_pack_int8
   m->flags &= ~kPairs;  // and so is the FwFM pair list
   for (int h = 0; h < m->H; ++h) m->lin_w[h] = lin_w ? lin_w[h] : nullptr;
   return DFWFM_OK;
@@ -1151,6 +1158,127 @@ int dfwfm_bf16_fused_forward_batches(dfwfm_model* m, int32_t nb, const int64_t* 
 int dfwfm_bf16_fused_forward(dfwfm_model* m, const int64_t* xi, int64_t xi_stride, const float* xv,
                              int64_t xv_stride, int64_t batch, float* out, void* stream) {
   return dfwfm_bf16_fused_forward_batches(m, 1, &xi, xi_stride, &xv, xv_stride, batch, &out, stream);
+}
+
+// The int8 deep tower in one launch (include/dfwfm_int8.h, dfwfm_int8.hip)
+int dfwfm_int8_abi_version(void) { return DFWFM_INT8_ABI_VERSION; }
+
+}  // extern "C"
+
+namespace {
+
+// the model's shape (the fused bf16 forward's set), and the gather's FwFM in the pieces form (no pair list)
+bool int8_ok(const dfwfm_model* m) {
+  return m->cfg.use_deep && int8_supported(m->F, m->D, m->H, m->NT) && m->MT <= 3 && !(m->flags & kPairs) &&
+         int8_lds_bytes(16, m->F, m->D, m->NT, m->W0) <= 160 * 1024;
+}
+
+// Rows per workgroup for a launch of `rows` rows: fused_rows' rule (16 rows while they are at most one workgroup per
+// CU, 32 from there on); DFWFM_DIAG int8rows=16 / 32 forces one (tests, A/B).  The logits do not depend on it.
+int int8_rows(dfwfm_model* m, int64_t rows) {
+  const int forced = diag_opt("int8rows", 0);
+  int64_t cus;
+  {  // the device's CUs (queried at the model's first call, so later calls are capturable into a graph)
+    std::lock_guard<std::mutex> lock(g_cu_mu);
+    if (m->dev_cus == 0) {
+      hipDeviceProp_t prop;
+      m->dev_cus = hipGetDeviceProperties(&prop, m->device) == hipSuccess ? prop.multiProcessorCount : 256;
+    }
+    cus = m->dev_cus;
+  }
+  const bool fits32 = int8_lds_bytes(32, m->F, m->D, m->NT, m->W0) <= 160 * 1024;
+  if (forced == 32) return fits32 ? 32 : 16;
+  if (forced == 0 && (rows + 15) / 16 > cus && fits32) return 32;
+  return 16;
+}
+
+int int8_check(dfwfm_model* m) {
+  if (!m->cfg.use_deep) return fail(DFWFM_ERR_UNSUPPORTED, "int8 forward: the model has no deep tower");
+  if (!int8_ok(m))
+    return fail(DFWFM_ERR_UNSUPPORTED,
+                "int8 forward: shape not supported (embedding_size 10, field_size <= 48, deep_nodes <= 512, no FwFM "
+                "pair list)");
+  return DFWFM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dfwfm_model_pack_int8(dfwfm_model* m, void* stream) {
+  if (!m) return fail(DFWFM_ERR_INVALID_ARG, "null model");
+  m->int8_on = false;
+  if (!m->cfg.use_deep) return fail(DFWFM_ERR_UNSUPPORTED, "int8 pack: the model has no deep tower");
+  if (!int8_supported(m->F, m->D, m->H, m->NT) || m->MT > 3)
+    return fail(DFWFM_ERR_UNSUPPORTED,
+                "int8 pack: shape not supported (embedding_size 10, field_size <= 48, deep_nodes <= 512)");
+  if (!m->dense_set) return fail(DFWFM_ERR_STATE, "set_dense must precede pack_int8");
+  for (int h = 0; h < m->H; ++h)
+    if (!m->lin_w[h]) return fail(DFWFM_ERR_STATE, "set_dense must precede pack_int8");
+  if (!m->d_wi8) {
+    int rc = dev_alloc(&m->d_wi8, int8_pack_bytes(m->F, m->D, m->H, m->NT));
+    if (rc != DFWFM_OK) return rc;
+  }
+  if (!m->d_i8s) {
+    int rc = dev_alloc(&m->d_i8s, (size_t)2 * m->H * m->NT * 16);
+    if (rc != DFWFM_OK) return rc;
+  }
+  // the layers' source pointers travel as kernel arguments: nothing staged from the stack, no synchronisation
+  hipError_t e = launch_int8_pack(m->lin_w, m->d_mlp_b, m->d_wi8, m->d_i8s, m->d_i8s + (size_t)m->H * m->NT * 16,
+                                  m->H, m->N, m->F, m->D, m->NT, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "int8 pack launch");
+  m->int8_on = true;
+  return DFWFM_OK;
+}
+
+int dfwfm_int8_supported(dfwfm_model* m, int* supported) {
+  if (!m || !supported) return fail(DFWFM_ERR_INVALID_ARG, "null argument");
+  *supported = int8_ok(m) ? 1 : 0;
+  return DFWFM_OK;
+}
+
+int dfwfm_int8_forward_batches(dfwfm_model* m, int32_t nb, const int64_t* const* xi, int64_t xi_stride,
+                               const float* const* xv, int64_t xv_stride, int64_t batch, float* const* out,
+                               void* stream) {
+  if (!m) return fail(DFWFM_ERR_INVALID_ARG, "null model");
+  if (nb < 0) return fail(DFWFM_ERR_INVALID_ARG, "negative batch count");
+  int rc = int8_check(m);
+  if (rc != DFWFM_OK) return rc;
+  if (nb == 0) return DFWFM_OK;
+  if (!xi || !xv || !out) return fail(DFWFM_ERR_INVALID_ARG, "null pointer array");
+  for (int32_t i = 0; i < nb; ++i)
+    if ((rc = check_inputs(m, xi[i], xi_stride, xv[i], xv_stride, batch, out[i])) != DFWFM_OK) return rc;
+  if (!m->int8_on)
+    return fail(DFWFM_ERR_STATE, "int8 forward: the int8 pack is absent or stale (dfwfm_model_pack_int8)");
+  if (batch == 0) return DFWFM_OK;
+  // the tile for the first launch's rows (a set of up to kMaxSet batches); later launches of a larger set use it too
+  const int rows = int8_rows(m, (int64_t)(nb < kMaxSet ? nb : kMaxSet) * batch);
+  const int64_t tiles = (batch + rows - 1) / rows;
+  if ((int64_t)(nb < kMaxSet ? nb : kMaxSet) * tiles > 0x7fffffff)
+    return fail(DFWFM_ERR_UNSUPPORTED, "batch too large for the int8 forward");
+  for (int32_t i0 = 0; i0 < nb; i0 += kMaxSet) {
+    const int32_t n = nb - i0 < kMaxSet ? nb - i0 : kMaxSet;
+    FwdArgs a;
+    fill_forward_args(m, a, xi[i0], xi_stride, xv[i0], xv_stride, batch, out[i0]);
+    if (n > 1) {
+      a.nb = n;
+      a.tiles = (int32_t)tiles;
+      for (int32_t j = 0; j < n; ++j) {
+        a.set_xi[j] = xi[i0 + j];
+        a.set_xv[j] = xv[i0 + j];
+        a.set_out[j] = out[i0 + j];
+      }
+    }
+    const hipError_t e = launch_int8_fused(a, m->d_wi8, m->d_i8s, m->d_i8s + (size_t)m->H * m->NT * 16, rows,
+                                           (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "int8 forward launch");
+  }
+  return DFWFM_OK;
+}
+
+int dfwfm_int8_forward(dfwfm_model* m, const int64_t* xi, int64_t xi_stride, const float* xv, int64_t xv_stride,
+                       int64_t batch, float* out, void* stream) {
+  return dfwfm_int8_forward_batches(m, 1, &xi, xi_stride, &xv, xv_stride, batch, &out, stream);
 }
 
 // The folded layer 1 of the one-launch bf16 forward (include/dfwfm_bf16_fold.h)

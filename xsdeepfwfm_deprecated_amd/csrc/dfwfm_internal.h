@@ -141,7 +141,7 @@ inline unsigned fwd_grid(const FwdArgs& a, int rows) {
 // generic kernel for MLP-free models), p3ng (4 / 8: MLP-free waves), bf16tile (0 / 1 / 2 / 3: the bf16 tower's tile per
 // wave, 16 x 16 / 16 x 80 / 32 x 80 / 32 x 80 with the weights in LDS; same logits), bf16rows (16 / 32 / 64: rows per
 // workgroup of the fused bf16 forward; same logits), bf16fold (0: dfwfm_model_fold_bf16 leaves the fused bf16 forward
-// unfolded), stamps / ring / ft / bwd / scatter /
+// unfolded), int8rows (16 / 32: rows per workgroup of the int8 forward; same logits), stamps / ring / ft / bwd / scatter /
 // drop_flags (phase stamps and phase-skip bits; results invalid).  dflt when the key is absent.
 inline int diag_opt(const char* key, int dflt) {
   const char* s = getenv("DFWFM_DIAG");
@@ -461,6 +461,26 @@ hipError_t launch_bf16_fused(const FwdArgs& a, const uint16_t* wb, const uint16_
 // of the numerical fields' second-order tables (the device descriptors)
 hipError_t launch_bf16_fold_pack(const float* w1, const FieldDev* fields, uint16_t* dst, int N, int F, int D, int num,
                                  int NT, hipStream_t s);
+
+// The forward with an int8 deep tower in one launch (dfwfm_int8.hip, include/dfwfm_int8.h): the fused bf16 forward's
+// shape (16 or 32 rows per workgroup, FwdArgs with batch sets) on v_mfma_i32_16x16x64_i8, the weights from the pack of
+// launch_int8_pack: per layer [NT][KC][64 lanes][16 int8], K steps of 64, beside it the per-neuron scales and biases.
+struct Int8Geo {
+  const int8_t* w;     // the int8 pack: layer 1 [NT][KC0][64][16], then layers 2..H [NT][KCN][64][16] each
+  const float* sw;     // [H][NT*16] weight scales per neuron (1 for padded neurons)
+  const float* b;      // [H][NT*16] biases
+  int32_t KC0, KCN;    // K steps of 64 of layer 1 and of the later layers
+  int32_t WE;          // f32 E tile columns that hold data or zeros
+  int32_t SE, SQ;      // LDS row strides: f32 E tile (floats), int8 tile (bytes)
+};
+bool int8_supported(int F, int D, int H, int NT);
+size_t int8_pack_bytes(int F, int D, int H, int NT);
+size_t int8_lds_bytes(int rows, int F, int D, int NT, int W0);
+// one launch: the pack, sw and b (b copied from the padded biases mlp_b of set_dense) from the row-major f32 weights
+hipError_t launch_int8_pack(const float* const* w, const float* mlp_b, int8_t* dst, float* sw, float* b, int H, int N,
+                            int F, int D, int NT, hipStream_t s);
+hipError_t launch_int8_fused(const FwdArgs& a, const int8_t* w, const float* sw, const float* b, int rows,
+                             hipStream_t s);
 
 // dW_l += G_l^T X_{l-1} and db_l += sum_b G_l for every layer in one launch.
 struct DwArgs {

@@ -77,6 +77,9 @@ class ForwardEngine:
         # ... and its one-launch form (forward_bf16_fused) instead, when DeepFMs.bf16_fused asks for it and the shape
         # is supported (DeepFMs sets it: bf16_fused and bf16_fused_supported())
         self.bf16_fused = False
+        # forward() takes the int8 deep tower (forward_int8) for every B > 0, ahead of everything else; the caller
+        # keeps the int8 pack current with sync_int8 (DeepFMs sets it from its mlp_dtype)
+        self.int8 = False
 
     def close(self):
         if self.handle is not None and self.handle.value:
@@ -138,6 +141,7 @@ class ForwardEngine:
         self._pairs_key = None
         self._sparse_key = None
         self._bf16_key = None
+        self._int8_key = None
         self._fold_key = None  # the folded layer 1: built from W1 and the numerical tables' row 0
         self._bf16_fold_key = None  # ... and the bf16 tower's (sync_bf16_fold)
 
@@ -213,6 +217,19 @@ class ForwardEngine:
         self._bf16_fold_key = None  # dfwfm_model_pack_bf16 turns the folded layer 1 off
         return bool(enable)
 
+    def sync_int8(self, on: bool = True) -> bool:
+        """dfwfm_model_pack_int8 (include/dfwfm_int8.h): (re)build the int8 pack of the hidden layers (weights, per-neuron
+        scales, biases) when the dense parameters changed (one launch, stream-ordered, no host synchronisation).
+        Returns whether the int8 path is on; on=False packs nothing."""
+        if not on:
+            return False
+        key = self._dense_key
+        if key is None or key != getattr(self, "_int8_key", None):
+            _lib.check(_lib.lib().dfwfm_model_pack_int8(self.handle, _stream_handle(self.device)),
+                       "dfwfm_model_pack_int8")
+            self._int8_key = key
+        return True
+
     def sync_bf16_fold(self, tables, enable: bool = True) -> bool:
         """dfwfm_model_fold_bf16 (include/dfwfm_bf16_fold.h): (re)build the folded layer 1 of forward_bf16_fused /
         forward_bf16_batches after a weight update or a sync_bf16 (stream-ordered, no host synchronisation), or turn
@@ -231,6 +248,8 @@ class ForwardEngine:
     # -- hot path ----------------------------------------------------------
     def forward(self, xi: torch.Tensor, xv: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
         B = xi.shape[0]
+        if self.int8 and B > 0:
+            return self.forward_int8(xi, xv, out)
         if self.bf16 and B > 0:
             return self.forward_bf16_fused(xi, xv, out) if self.bf16_fused else self.forward_bf16(xi, xv, out)
         if 0 < B <= self.small_rows:
@@ -380,6 +399,46 @@ class ForwardEngine:
         rc = _lib.lib().dfwfm_bf16_fused_forward_batches(self.handle, nb, pxi, xs, pxv, vs, B, pout,
                                                          _stream_handle(self.device))
         _lib.check(rc, "dfwfm_bf16_fused_forward_batches")
+        return outs
+
+    def int8_supported(self) -> bool:
+        """dfwfm_int8_supported: whether forward_int8 / forward_int8_batches run this model (its shape, and no FwFM
+        pair list on); host-only."""
+        v = ctypes.c_int(0)
+        _lib.check(_lib.lib().dfwfm_int8_supported(self.handle, ctypes.byref(v)), "dfwfm_int8_supported")
+        return bool(v.value)
+
+    def forward_int8(self, xi: torch.Tensor, xv: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+        """dfwfm_int8_forward (include/dfwfm_int8.h): the forward with the hidden layers on int8 MFMA (weights
+        quantized per neuron, activations per row and layer; gather, first order and FwFM in exact f32) in one launch,
+        after sync_int8(True).  DfwfmError for a shape int8_supported() refuses.  A row's bits do not depend on the
+        batch around it."""
+        B = xi.shape[0]
+        ncat = self.cfg["field_size"] - self.cfg["numerical"]
+        num = self.cfg["numerical"]
+        _require_rows(xi, "Xi", torch.int64, self.device, ncat)
+        _require_rows(xv, "Xv", torch.float32, self.device, num)
+        if out is None:
+            out = torch.empty(B, dtype=torch.float32, device=self.device)
+        elif out.numel() < B:
+            raise ValueError("forward_int8: output smaller than the batch")
+        xs = xi.stride(0) if ncat > 0 else 0
+        vs = xv.stride(0) if num > 0 else 0
+        rc = _lib.lib().dfwfm_int8_forward(self.handle, ctypes.c_void_p(xi.data_ptr()), xs,
+                                           ctypes.c_void_p(xv.data_ptr()), vs, B,
+                                           ctypes.c_void_p(out.data_ptr()), _stream_handle(self.device))
+        _lib.check(rc, "dfwfm_int8_forward")
+        return out
+
+    def forward_int8_batches(self, batches, outs) -> list:
+        """dfwfm_int8_forward_batches: forward_int8 of every (xi, xv) in `batches` (same batch size and row strides),
+        one launch per 32 batches; logits into outs[i], bit-identical to forward_int8 on each batch alone."""
+        if len(batches) == 0:
+            return outs
+        nb, B, xs, vs, pxi, pxv, pout = self._batch_set_args(batches, outs, "forward_int8_batches")
+        rc = _lib.lib().dfwfm_int8_forward_batches(self.handle, nb, pxi, xs, pxv, vs, B, pout,
+                                                   _stream_handle(self.device))
+        _lib.check(rc, "dfwfm_int8_forward_batches")
         return outs
 
     def forward_batches(self, batches, outs) -> list:
