@@ -35,6 +35,11 @@ from xsdeepfwfm_deprecated_amd import synth  # noqa: E402
 SMALL_SIZES = [1] * 13 + [1458, 556, 2451, 1661, 306, 20, 1205, 634, 4, 463, 522, 2434, 317, 27, 1174, 2253,
                           11, 472, 205, 5, 2386, 18, 16, 678, 89, 509]
 
+# the same layout with the categorical tables at the row counts where the kernels change path (tests/table_cases.py:
+# the table zoo's 16) and ten more either side of powers of two and of qr_threshold, all below 2500
+ZOO_SIZES = [1] * 13 + [1, 2, 63, 64, 65, 127, 128, 129, 200, 201, 255, 256, 257, 449, 1000, 1031,
+                        3, 202, 203, 511, 512, 513, 777, 2047, 2048, 2499]
+
 BASE = dict(field_size=39, numerical=13, embedding_size=10, use_fwfm=1, use_fm=0, use_logit=0, use_deep=1,
             use_lw=1, use_fwlw=0, h_depth=3, deep_nodes=400, embedding_bag=0, qr_flag=0,
             qr_operation="mult", qr_collisions=4, qr_threshold=200, seed=1234, input_seed=0, batch=256)
@@ -58,6 +63,12 @@ CONFIGS = {
     "fm_deep": dict(use_fwfm=0, use_fm=1),
     "logit": dict(use_fwfm=0, use_logit=1, use_deep=0, use_lw=0),
     "tiny_deepfwfm_lw": dict(data="tiny", batch=2000),
+    # QR geometry away from c = 4: one remainder row; c dividing almost no n ("add"); c > n (one quotient row).  Rows
+    # 0 .. 2 of Xi are forced to 0, n - 1 and the last index a QR field accepts, ceil(n / c) c - 1 >= n
+    "zoo_qr_mult_c1": dict(embedding_bag=1, qr_flag=1, qr_collisions=1, sizes=ZOO_SIZES, edge_rows=1),
+    "zoo_qr_add_c7": dict(embedding_bag=1, qr_flag=1, qr_collisions=7, qr_operation="add", sizes=ZOO_SIZES,
+                          edge_rows=1),
+    "zoo_qr_mult_c5000": dict(embedding_bag=1, qr_flag=1, qr_collisions=5000, sizes=ZOO_SIZES, edge_rows=1),
 }
 
 
@@ -65,7 +76,7 @@ def make_cfg(name):
     cfg = dict(BASE)
     cfg.update(CONFIGS[name])
     cfg["name"] = name
-    cfg["feature_sizes"] = tiny_sizes() if cfg.get("data") == "tiny" else list(SMALL_SIZES)
+    cfg["feature_sizes"] = tiny_sizes() if cfg.get("data") == "tiny" else list(cfg.pop("sizes", SMALL_SIZES))
     return cfg
 
 
@@ -158,6 +169,10 @@ def inputs(cfg):
         assert xi.shape[1] == ncat
         return xi, xv, y
     xi, xv = synth.synth_inputs(cfg["feature_sizes"], cfg["numerical"], cfg["batch"], seed=cfg["input_seed"])
+    if cfg.get("edge_rows"):
+        n, c = np.asarray(cfg["feature_sizes"][cfg["numerical"]:], np.int64), cfg["qr_collisions"]
+        isqr = (n > cfg["qr_threshold"]) & bool(cfg["qr_flag"])
+        xi[0], xi[1], xi[2] = 0, n - 1, np.where(isqr, -(-n // c) * c - 1, n - 1)
     y = synth.synth_labels(cfg["batch"], seed=cfg["input_seed"])
     return xi, xv, y
 

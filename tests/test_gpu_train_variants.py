@@ -27,6 +27,9 @@ kernels (tests/test_train_variants.py).
     dropout p = 0.1   3.7e-7 / 4.5e-7      3.7e-7 / 5.0e-7      3.3e-7 / 6.4e-7
     dropout p = 0.9   3.5e-7 / 1.4e-6      9.3e-7 / 1.9e-6      1.0e-6 / 2.3e-6
 
+The table zoo's cases (zoo_*, zoo39_*: tests/table_cases.py) run here too; their figures are in the table of
+tests/test_gpu_train_tables.py.
+
 The per-row figure only means something on well-conditioned samples (train_cases.SEEDS): a table row read by one
 sample carries that sample's (sigmoid(z) - y) / B, and with logits of size 1e2 the fp32 port itself is off by 1e-5 to
 100 % of such a row on most seeds.

@@ -14,26 +14,45 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+import table_cases
 from conftest import logit_close, logit_close_scaled, model_kwargs
 from oracle import torch_port
 
 G_TOL = 2e-5  # test_gpu_train.G_TOL / test_cpu_kernel.G_TOL: of a tensor's (here also: a row's) largest entry
 
 
-def train_case(F, num, D, N, H, kind="fwfm", deep=1, lw=1, fwlw=0, qr=0, op="mult", embbag=0, B=37, seed=11):
+def edge_rows(cfg, xi):
+    """xi with its first three rows forced to the ends of every table's index range: row 0 all 0, row 1 n - 1 per
+    field, row 2 the last index a QR field accepts, ceil(n / c) c - 1 (>= n when c does not divide n: the quotient
+    table's last row; QREmbeddingBag rejects only i // c >= ceil(n / c)), and n - 1 for a plain field."""
+    num, c = cfg["numerical"], cfg["qr_collisions"]
+    n = np.asarray(cfg["feature_sizes"][num:], np.int64)
+    isqr = (n > cfg["qr_threshold"]) & bool(cfg["qr_flag"])
+    xi = xi.copy()
+    xi[0], xi[1], xi[2] = 0, n - 1, np.where(isqr, -(-n // c) * c - 1, n - 1)
+    return xi
+
+
+def train_case(F, num, D, N, H, kind="fwfm", deep=1, lw=1, fwlw=0, qr=0, op="mult", embbag=0, B=37, seed=11,
+               sizes=None, c=4, threshold=200, edges=False):
     """(cfg, params, xi, xv, y): test_gpu_parity._sweep_case over the model kinds.  B = 37 is two full 16-row tiles
     and a ragged 5; the tables (50 .. 449 rows) are small enough that a batch hits some rows twice and leaves most
-    untouched."""
+    untouched.  sizes: the categorical tables' row counts instead; c, threshold: qr_collisions, qr_threshold;
+    edges: rows 0 .. 2 are edge_rows' (tests/table_cases.py: the table zoo)."""
     from xsdeepfwfm_deprecated_amd import DeepFMs, synth
-    sizes = [1] * num + [int(x) for x in 50 + (np.arange(F - num) * 37) % 400]
+    cat = [int(x) for x in 50 + (np.arange(F - num) * 37) % 400] if sizes is None else [int(x) for x in sizes]
+    assert len(cat) == F - num
+    sizes = [1] * num + cat
     cfg = dict(field_size=F, feature_sizes=sizes, embedding_size=D, use_fwfm=int(kind == "fwfm"),
                use_fm=int(kind == "fm"), use_logit=int(kind == "logit"), use_deep=int(deep), use_lw=int(lw),
                use_fwlw=int(fwlw), h_depth=H, deep_nodes=N, numerical=num, embedding_bag=int(embbag), qr_flag=int(qr),
-               qr_operation=op, qr_collisions=4, qr_threshold=200)
+               qr_operation=op, qr_collisions=int(c), qr_threshold=int(threshold))
     m = DeepFMs(**model_kwargs(cfg))
     shapes = {k: tuple(v.shape) for k, v in m.state_dict().items()}
     params = synth.synth_state(shapes, F, D, N, kind in ("fwfm", "fm"), bool(deep), seed=seed)
     xi, xv = synth.synth_inputs(sizes, num, B, seed=seed)
+    if edges:
+        xi = edge_rows(cfg, xi)
     y = (np.arange(B) % 3 == 0).astype(np.float32)
     return cfg, params, xi, xv, y
 
@@ -170,9 +189,24 @@ SEEDS = {"fm_deep": 16, "fm_deep_nolw": 33, "fm_shallow": 16, "logit": 33, "fwfm
          "logit_num20": 33}
 
 
+# The table zoo (tests/table_cases.py): tables at the row counts where the scatter kernels switch paths, QR collision
+# counts c that put the remainder table at the same switch points, the forced edge rows included.  Seeds by the same
+# rule, forced rows included (and for c <= 7 every remainder row read by the 37 samples: table_cases.check_inputs).
+CASES.update({table_cases.name(op, c): table_cases.train_kwargs(op, c)
+              for op in table_cases.OPS for c in table_cases.C_ALL})
+# 14 to 29 of the seeds 1 .. 60 qualify per (c, op); 20 is the one that does for all sixteen.
+SEEDS.update({name: 20 for name in CASES if name.startswith("zoo_")})
+# The 39-field zoo (table_cases.WIDE: the smallest shape the helper-wave training forward takes) over C_FEW: 2 to 17
+# seeds qualify per case and none for all six; each case gets its own with the smallest per-row figure.
+CASES.update({table_cases.name(op, c, True): table_cases.train_kwargs(op, c, True)
+              for op in table_cases.OPS for c in table_cases.C_FEW})
+SEEDS.update({"zoo39_mult_c1": 36, "zoo39_mult_c7": 44, "zoo39_mult_c129": 47, "zoo39_add_c1": 9, "zoo39_add_c7": 12,
+              "zoo39_add_c129": 25})
+
 RAGGED = [(name, B) for name in ("num0", "allnum", "logit") for B in (1, 16, 17)]
 DROPOUT_RATES = (0.1, 0.9)
-FUSED = ("fm_deep", "qr_add", "num0", "allnum")
+FUSED = ("fm_deep", "qr_add", "num0", "allnum") + tuple(table_cases.name(op, c) for c in table_cases.C_FEW
+                                                       for op in table_cases.OPS)
 
 
 @functools.lru_cache(maxsize=None)
