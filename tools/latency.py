@@ -8,6 +8,7 @@ batch's forward is also replayed from a one-forward hipGraph (launch overhead of
 Prints one JSON line.
 
   python tools/latency.py [--calls 1000] [--batches 1,16,64,256,1024,4096,8192] [--small] [--bf16] [--bf16-fused] [--int8]
+  python tools/latency.py --half-tables [--rounds 7]
 
 --small: the small-batch serving forward (eng.forward_small, include/dfwfm_serve.h) measured beside eng.forward at
 every batch, same figures, under models["deepfwfm_small"] (the batch where it stops winning is the value to give
@@ -30,6 +31,14 @@ behind the unfolded ones at every batch, same figures, under models["deepfwfm_bf
 eng.forward_bf16_fused with --bf16-fused) in the same process at every batch, same figures, under
 models["deepfwfm_int8"]; and the batch-set leg through eng.forward_int8_batches: forward_int8_batches_4096_us and
 forward_int8_batches_4096_us_per_batch in that row.  DFWFM_DIAG int8rows=16|32 forces its row tile (A/B).
+
+--half-tables: a measurement of its own (nothing above runs): the f32 serving copy of the categorical tables against
+the fp16 one (DeepFMs.table_dtype, include/dfwfm_half_tables.h), two modules with the same weights in one process,
+the two timed in turns (--rounds turns each, the median and the min-max spread reported), every call replayed from a
+hipGraph so that launch overhead is not what is compared.  Rows, in us per 4096-row batch: the FwFM-only forward lone
+and as a 20-batch set, the deep f32 forward, the fused bf16 forward and the int8 forward as 20-batch sets -- at the
+Criteo-39 table sizes and with every categorical table 8 times as long (HBM-resident).  Also the copies' bytes and
+the pack time.
 """
 import argparse
 import json
@@ -123,6 +132,103 @@ def measure_batch_set(call, xi, xv, out, dev, reps=10):
     return e0.elapsed_time(e1) * 1e3 / reps, nb
 
 
+def half_tables(rounds, dev):
+    """--half-tables: see the module docstring."""
+    from xsdeepfwfm_deprecated_amd import DeepFMs, synth
+    B, NB = 4096, 20
+    res = {"what": "f32 serving copy of the categorical tables against the fp16 one (DeepFMs.table_dtype), us per "
+                   "4096-row batch, hipGraph replays, the two copies timed in turns; median [min, max] over rounds",
+           "rounds": rounds, "batch": B, "set": NB, "scales": {}}
+
+    def module(sizes, deep, dtype):
+        m = DeepFMs(field_size=39, feature_sizes=sizes, embedding_size=10, use_fwfm=1, use_fm=0, use_deep=deep,
+                    use_lw=1, numerical=13, use_cuda=True)
+        shapes = {k: tuple(v.shape) for k, v in m.state_dict().items()}
+        params = synth.synth_state(shapes, 39, 10, 400, True, bool(deep), seed=1234)
+        m.load_state_dict({k: torch.from_numpy(v) for k, v in params.items()})
+        m = m.to(dev).eval()
+        m.strict_index_check = False
+        m.table_dtype = dtype
+        return m
+
+    def graph_of(fn, n):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize(dev)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            for _ in range(n):
+                fn()
+        torch.cuda.synchronize(dev)
+        return g
+
+    def timed(g, n, reps):
+        st = torch.cuda.current_stream(dev)
+        g.replay()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        for _ in range(reps):
+            g.replay()
+        e1.record(st)
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / (reps * n)
+
+    def summary(v):
+        return {"median": round(float(np.median(v)), 3), "min": round(float(min(v)), 3), "max": round(float(max(v)), 3)}
+
+    for scale in (1, 8):
+        sizes = [1] * 13 + [int(n) * scale for n in synth.CRITEO_FEATURE_SIZES[13:]]
+        host = [synth.synth_inputs(sizes, 13, B, seed=7 + i) for i in range(NB)]
+        dev_in = [(torch.from_numpy(xi).to(dev), torch.from_numpy(xv).to(dev)) for xi, xv in host]
+        outs = [torch.empty(B, dtype=torch.float32, device=dev) for _ in range(NB)]
+        sc = {"categorical_rows": int(sum(sizes[13:])), "table_bytes": int(sum(sizes[13:])) * 44, "copy_bytes": {},
+              "pack_ms": {}, "us_per_batch": {}}
+        with torch.no_grad():
+            for deep in (0, 1):
+                graphs = {}  # row -> {dtype: (graph, calls in it, batches per call)}
+                keep = []
+                for dtype in ("f32", "fp16"):
+                    m = module(sizes, deep, dtype)
+                    keep.append(m)
+                    eng = m._sync_inference(dev)
+                    torch.cuda.synchronize(dev)
+                    ts = []
+                    for _ in range(3):  # the pack alone: one launch and the wait dfwfm_model_pack_tables[_half] makes
+                        eng._packed_key = None
+                        t0 = time.perf_counter()
+                        m._sync_inference(dev)
+                        torch.cuda.synchronize(dev)
+                        ts.append(time.perf_counter() - t0)
+                    sc["pack_ms"][dtype] = round(float(np.median(ts)) * 1e3, 3)
+                    sc["copy_bytes"][dtype] = eng.serving_copy_bytes()
+                    calls = {}
+                    if not deep:
+                        calls["fwfm_lone"] = (lambda e=eng: e.forward(dev_in[0][0], dev_in[0][1], outs[0]), 20, 1)
+                        calls["fwfm_set20"] = (lambda e=eng: e.forward_batches(dev_in, outs), 5, NB)
+                    else:
+                        eng.sync_bf16(True)
+                        eng.sync_int8(True)
+                        if not (eng.bf16_fused_supported() and eng.int8_supported()):
+                            raise RuntimeError("the Criteo-39 model must run the fused bf16 and int8 forwards")
+                        calls["deep_f32_set20"] = (lambda e=eng: e.forward_batches(dev_in, outs), 2, NB)
+                        calls["deep_bf16_fused_set20"] = (lambda e=eng: e.forward_bf16_batches(dev_in, outs), 2, NB)
+                        calls["deep_int8_set20"] = (lambda e=eng: e.forward_int8_batches(dev_in, outs), 2, NB)
+                    for row, (fn, n, per) in calls.items():
+                        graphs.setdefault(row, {})[dtype] = (graph_of(fn, n), n, per)
+                for row, by in graphs.items():
+                    t = {"f32": [], "fp16": []}
+                    for _ in range(rounds):
+                        for dtype in ("f32", "fp16"):
+                            g, n, per = by[dtype]
+                            t[dtype].append(timed(g, n, 20) / per)
+                    sc["us_per_batch"][row] = {"f32": summary(t["f32"]), "fp16": summary(t["fp16"]),
+                                               "fp16_over_f32": round(float(np.median(t["fp16"]) / np.median(t["f32"])), 4)}
+                del graphs, keep
+                torch.cuda.empty_cache()
+        res["scales"][str(scale)] = sc
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=1000)
@@ -133,7 +239,14 @@ def main():
                     help="also measure eng.forward_bf16_fused and eng.forward_bf16_batches (deep model; implies --bf16)")
     ap.add_argument("--int8", action="store_true",
                     help="also measure eng.forward_int8 and eng.forward_int8_batches (deep model)")
+    ap.add_argument("--half-tables", action="store_true",
+                    help="only this: the f32 serving copy of the tables against the fp16 one (see the docstring)")
+    ap.add_argument("--rounds", type=int, default=7, help="--half-tables: timed turns per copy and row")
     a = ap.parse_args()
+    if a.half_tables:
+        dev = torch.device("cuda", 0)
+        torch.cuda.set_device(dev)
+        return half_tables(a.rounds, dev)
     a.bf16 = a.bf16 or a.bf16_fused
     batches = [int(x) for x in a.batches.split(",")]
     if not batches or min(batches) < 1 or max(batches) > 81920:

@@ -108,6 +108,14 @@ class DeepFMs(nn.Module):
         # first-order weight in one aligned row, dfwfm_model_pack_tables), rebuilt after weight updates; the values
         # are copied, so the logits are the same bits either way
         self.pack_tables = True
+        # storage of the serving copy's second-order rows: "f32" (default), or "fp16" -- each categorical second-order
+        # value rounded to IEEE fp16 once when the copy is built, the first-order weight kept f32, half the bytes per
+        # row (include/dfwfm_half_tables.h).  The logits are those of the same path on a model
+        # whose categorical second-order tables are w.half().float().  Inference on a HIP device only; training reads
+        # the f32 tables.  One path, no fallback: a model the copy does not cover (QR fields, fwlw without first-order
+        # tables), pack_tables = False, a CPU module, small_batch_rows > 0, the per-layer bf16 forward, a sparse deep
+        # tower or a value that overflows fp16 raise DfwfmError rather than serve unrounded rows
+        self.table_dtype = "f32"
         # the fused inference forward folds the numerical fields into layer 1 of the deep tower (their embedding is
         # Xv * v_f[0], so layer 1 takes Xv * P with P = W1 v_f[0] precomputed after each weight update: 18 K chunks
         # instead of 25 at Criteo-39; include/dfwfm_fold.h).  A re-association of f32 sums:
@@ -298,7 +306,15 @@ class DeepFMs(nn.Module):
             for f in range(self.num, self.field_size):
                 d = self._field_desc(None if second is None else second[f], None if first is None else first[f])
                 tabs.append((d["emb2"], d["emb1"]))
-            eng.sync_packed(tabs, self.pack_tables)
+            if self._half_tables():
+                if not self.pack_tables:
+                    raise DfwfmError("table_dtype='fp16' is the serving copy's storage: it needs pack_tables = True")
+                if self.use_deep and int(getattr(self, "small_batch_rows", 0)) > 0:
+                    raise DfwfmError("table_dtype='fp16': the small-batch serving path (small_batch_rows > 0) is not "
+                                     "part of the fp16 tables' contract")
+                eng.sync_packed_half(tabs)
+            else:
+                eng.sync_packed(tabs, self.pack_tables)
             if self.use_deep:  # the folded layer 1, rebuilt when W1 or a numerical table changed
                 eng.sync_fold([second[f].weight.detach() for f in range(self.num)],
                               bool(getattr(self, "fold_numerical", True)))
@@ -309,7 +325,28 @@ class DeepFMs(nn.Module):
             if eng.bf16:  # the fused form's folded layer 1, rebuilt when W1, a numerical table or the bf16 copy changed
                 eng.sync_bf16_fold([second[f].weight.detach() for f in range(self.num)],
                                    bool(eng.bf16_fused and getattr(self, "bf16_fold", False)))
+            self._half_tables_paths(eng)
         return eng
+
+    def _half_tables(self) -> bool:
+        """Whether table_dtype asks for the fp16 serving copy (validated here: at the next forward)."""
+        dt = getattr(self, "table_dtype", "f32")
+        if dt not in ("f32", "fp16"):
+            raise ValueError(f"table_dtype must be 'f32' or 'fp16', got {dt!r}")
+        return dt == "fp16"
+
+    def _half_tables_paths(self, eng, settled=False):
+        """With table_dtype = 'fp16': refuse the forwards outside its contract; settled: the forward has synced the
+        pair list and the sparse tower (the sparse tower's state is current only then)."""
+        if not self._half_tables() or not self.use_deep:
+            return
+        if eng.bf16 and not eng.bf16_fused:
+            raise DfwfmError("table_dtype='fp16' with mlp_dtype='bf16' needs the one-launch form (bf16_fused = True "
+                             "on a shape it supports, no FwFM pair list): the per-layer bf16 forward is not part of "
+                             "the fp16 tables' contract")
+        if settled and not eng.int8 and not eng.bf16 and getattr(eng, "_sparse_on", False):
+            raise DfwfmError("table_dtype='fp16': the sparse deep tower (sparse_mlp_max_density > 0) reads the plain "
+                             "tables; it is not part of the fp16 tables' contract")
 
     def _mlp_bf16(self) -> bool:
         """Whether mlp_dtype asks for the bf16 deep tower (validated here: at the next forward)."""
@@ -401,6 +438,7 @@ class DeepFMs(nn.Module):
     # ---------------------------------------------------------------- forward
     def forward(self, Xi, Xv):
         device = self._device()
+        half = self._half_tables()  # (a bad table_dtype raises here, whatever the mode)
         eng = self._sync_engine(device)
         xi, xv = self._prep_inputs(Xi, Xv, device)
         needs_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
@@ -414,6 +452,9 @@ class DeepFMs(nn.Module):
         if device.type == "cpu" and getattr(self, "mlp_dtype", "f32") == "int8":
             raise DfwfmError("mlp_dtype='int8' is the HIP-only int8 MFMA path (include/dfwfm_int8.h); "
                              "a CPU model runs mlp_dtype='f32'")
+        if device.type == "cpu" and half:
+            raise DfwfmError("table_dtype='fp16' is the HIP serving copy's storage (include/dfwfm_half_tables.h); "
+                             "a CPU model runs table_dtype='f32'")
         if device.type != "cpu":  # (the host kernel has no serving copy or pruned-layout variants)
             self._sync_inference(device)  # the tables' serving copy, re-packed after weight updates
             if self.use_deep and eng.int8:
@@ -427,6 +468,7 @@ class DeepFMs(nn.Module):
             elif self.use_fwfm:
                 if eng.sync_pairs(self.fwfm_pair_max):  # a pair list: the fused bf16 kernel does not run it
                     eng.bf16_fused = False
+            self._half_tables_paths(eng, settled=True)
         params = [q for q in self.parameters() if q.requires_grad]
         out, _ = torch.ops.dfwfm.forward(torch_ops.register(self), xi, xv, params, False, 0.0, 0)
         if self.strict_index_check and not self._defer_index_check:

@@ -42,7 +42,8 @@ HEADERS = ["dfwfm_internal.h", "dfwfm_device.h", "dfwfm_adam.h", os.path.join(".
            os.path.join("..", "..", "include", "dfwfm_serve.h"), os.path.join("..", "..", "include", "dfwfm_bf16.h"),
            os.path.join("..", "..", "include", "dfwfm_bf16_fused.h"), os.path.join("..", "..", "include", "dfwfm_fold.h"),
            os.path.join("..", "..", "include", "dfwfm_bf16_fold.h"), os.path.join("..", "..", "include", "dfwfm_int8.h"),
-           os.path.join("..", "..", "include", "dfwfm_lazy_adam.h")]
+           os.path.join("..", "..", "include", "dfwfm_lazy_adam.h"),
+           os.path.join("..", "..", "include", "dfwfm_half_tables.h")]
 ARCH = os.environ.get("DFWFM_OFFLOAD_ARCH", "gfx950")
 CPU_PATH = os.path.join(PKG_DIR, "libdfwfm_cpu.so")
 CPU_SOURCES = ["dfwfm_cpu.cpp"]
@@ -224,6 +225,15 @@ LAZY_ADAM_SIGNATURES = {
     "dfwfm_lazy_adam_step_dev": (ctypes.c_int, [ctypes.POINTER(dfwfm_lazy_adam_table), ctypes.c_int32, _P,
                                                 ctypes.c_int64, ctypes.c_int64, ctypes.c_double, ctypes.c_double,
                                                 ctypes.c_double, ctypes.c_double, ctypes.c_double, _P, _P]),
+}
+
+# the fp16 serving copy of the categorical tables (include/dfwfm_half_tables.h): same library, its own header and ABI
+# version
+HALF_TABLES_SIGNATURES = {
+    "dfwfm_half_tables_abi_version": (ctypes.c_int, []),
+    "dfwfm_model_pack_tables_half": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                                                    ctypes.POINTER(ctypes.c_int64), _P]),
+    "dfwfm_model_serving_copy_bytes": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int64)]),
 }
 
 _lib = None
@@ -461,6 +471,12 @@ def lib():
             fn.argtypes = args
         if L.dfwfm_int8_abi_version() != 1:
             raise DfwfmError("libdfwfm int8 ABI mismatch")
+        for name, (res, args) in HALF_TABLES_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        if L.dfwfm_half_tables_abi_version() != 1:
+            raise DfwfmError("libdfwfm half tables ABI mismatch")
         _lib = L
     return _lib
 

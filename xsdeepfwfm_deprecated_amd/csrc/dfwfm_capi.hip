@@ -19,6 +19,7 @@
 #include "../../include/dfwfm_int8.h"
 #include "../../include/dfwfm_fold.h"
 #include "../../include/dfwfm_lazy_adam.h"
+#include "../../include/dfwfm_half_tables.h"
 
 using namespace dfwfm;
 
@@ -58,6 +59,9 @@ struct dfwfm_model {
   size_t pkrows_floats;  // capacity
   const float** d_pk;    // [64] per-field row bases (device)
   int pkw;               // row stride in floats while the copy is in use, else 0
+  int pkh;               // 1 while the copy in use is the fp16 one (dfwfm_model_pack_tables_half), else 0
+  size_t pk_rows;        // rows of the copy in use
+  int32_t* d_pkovf;      // pack_tables_half: the count of values that round to +-inf
   int32_t npairs;
   int32_t* d_err;
   float4* d_wpack;
@@ -165,7 +169,7 @@ void free_model(dfwfm_model* m) {
   void* ptrs[] = {m->d_fields, m->d_upack, m->d_err,     m->d_wpack, m->d_mlp_b,   m->d_fc,  m->d_fwlw,
                   m->d_lw,     m->d_bias,  m->d_stamps,  m->d_wtpack, m->d_rsk,   m->d_ws,
                   m->d_ell,    m->d_cnt,   m->d_spstat, m->d_pairs, m->d_pkrows, m->d_pk,
-                  m->d_wbf16,  m->d_wbf16f, m->d_wi8,    m->d_i8s};
+                  m->d_wbf16,  m->d_wbf16f, m->d_wi8,    m->d_i8s,   m->d_pkovf};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   delete m;
@@ -417,6 +421,7 @@ int dfwfm_model_set_tables(dfwfm_model* m, const dfwfm_field_tables* t, int32_t 
     if (host[f].c > 0) host[f].n = (host[f].n + host[f].c - 1) / host[f].c * host[f].c;
   memcpy(m->h_fields, host, sizeof(FieldDev) * n);
   m->pkw = 0;  // the serving copy was built from the old tables
+  m->pkh = 0;
   m->fold_on = false;  // and so was the folded layer 1 (the numerical tables' row 0)
   m->bf16fold_on = false;
   m->flags &= ~kHasQR;
@@ -549,6 +554,7 @@ void fill_forward_args(const dfwfm_model* m, FwdArgs& a, const int64_t* xi, int6
   a.upack = m->d_upack;
   a.pk = m->pkw ? m->d_pk : nullptr;
   a.pkw = m->pkw;
+  a.pkh = m->pkh;
   a.pairs = m->d_pairs;
   a.npairs = m->npairs;
   a.fwlw = m->d_fwlw;
@@ -841,6 +847,8 @@ int dfwfm_forward_ws(dfwfm_model* m, const int64_t* xi, int64_t xi_stride, const
     return fail(DFWFM_ERR_INVALID_ARG, "workspace of %zu bytes < %zu (dfwfm_forward_workspace_bytes)", ws_bytes,
                 split_ws_bytes(m, batch));
   if (reinterpret_cast<uintptr_t>(workspace) % 16) return fail(DFWFM_ERR_INVALID_ARG, "workspace not 16-byte aligned");
+  if (m->pkh)  // its gather launch reads the plain tables: it would serve the unrounded rows
+    return fail(DFWFM_ERR_UNSUPPORTED, "the sparse deep tower does not read the fp16 serving copy");
   FwdArgs a;
   fill_forward_args(m, a, xi, xi_stride, xv, xv_stride, batch, out);
   a.part_stride = m->NC0 * 16;
@@ -1355,6 +1363,7 @@ int dfwfm_model_pack_tables(dfwfm_model* m, int32_t enable, int32_t* enabled, vo
   if (!m || !enabled) return fail(DFWFM_ERR_INVALID_ARG, "null argument");
   *enabled = 0;
   m->pkw = 0;
+  m->pkh = 0;
   if (!enable) return DFWFM_OK;
   if (!m->tables_set) return fail(DFWFM_ERR_STATE, "set_tables must precede pack_tables");
   const int need = kHasSecond | kNeedE | kFoTables;
@@ -1397,7 +1406,84 @@ int dfwfm_model_pack_tables(dfwfm_model* m, int32_t enable, int32_t* enabled, vo
   hipError_t e = launch_pack_tables(L, s);
   if (e != hipSuccess) return hip_fail(e, "pack tables launch");
   m->pkw = pkw;
+  m->pk_rows = rows;
   *enabled = 1;
+  return DFWFM_OK;
+}
+
+// The fp16 serving copy (include/dfwfm_half_tables.h): the rows of dfwfm_model_pack_tables with the second order in
+// fp16, in the same allocation.
+int dfwfm_half_tables_abi_version(void) { return DFWFM_HALF_TABLES_ABI_VERSION; }
+
+int dfwfm_model_pack_tables_half(dfwfm_model* m, int32_t enable, int32_t* enabled, int64_t* overflow_count,
+                                 void* stream) {
+  if (!m || !enabled) return fail(DFWFM_ERR_INVALID_ARG, "null argument");
+  *enabled = 0;
+  if (overflow_count) *overflow_count = 0;
+  m->pkw = 0;
+  m->pkh = 0;
+  if (!enable) return DFWFM_OK;
+  if (!m->tables_set) return fail(DFWFM_ERR_STATE, "set_tables must precede pack_tables_half");
+  const int need = kHasSecond | kNeedE | kFoTables;
+  if ((m->flags & need) != need || (m->flags & kHasQR) || m->F - m->num < 1) return DFWFM_OK;
+  const int pkw = half_row_bytes(m->D) / 4;  // the row stride, in floats as the gathers index it
+  PackTabList L;
+  memset(&L, 0, sizeof L);
+  L.D = m->D;
+  L.pkw = pkw;
+  size_t rows = 0;
+  for (int f = m->num; f < m->F; ++f) rows += (size_t)m->h_fields[f].n;
+  if (rows * pkw > m->pkrows_floats) {
+    if (m->d_pkrows) (void)hipFree(m->d_pkrows);
+    m->d_pkrows = nullptr;
+    m->pkrows_floats = 0;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&m->d_pkrows), rows * pkw * sizeof(float)));
+    m->pkrows_floats = rows * pkw;
+  }
+  if (!m->d_pk) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&m->d_pk), 64 * sizeof(float*)));
+  if (!m->d_pkovf) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&m->d_pkovf), sizeof(int32_t)));
+  const float* bases[64] = {};
+  size_t off = 0;
+  for (int f = m->num; f < m->F; ++f) {
+    const int j = f - m->num;
+    const int64_t n = m->h_fields[f].n;
+    bases[f] = m->d_pkrows + off;
+    L.emb2[j] = m->h_fields[f].emb2;
+    L.emb1[j] = m->h_fields[f].emb1;
+    L.dst[j] = m->d_pkrows + off;
+    L.n[j] = n;
+    const int64_t nb = (n + 255) / 256;
+    if ((int64_t)L.blk0[j] + nb > 0x7fffffff) return fail(DFWFM_ERR_UNSUPPORTED, "tables too large to pack");
+    L.blk0[j + 1] = L.blk0[j] + (int32_t)nb;
+    off += (size_t)n * pkw;
+  }
+  L.nf = m->F - m->num;
+  hipStream_t s = (hipStream_t)stream;
+  // one wait for everything: `bases` is a stack buffer, and the overflow count comes back behind the pack launch
+  int32_t over = 0;
+  hipError_t e = hipMemcpyAsync(m->d_pk, bases, sizeof bases, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemsetAsync(m->d_pkovf, 0, sizeof(int32_t), s);
+  if (e == hipSuccess) e = launch_pack_tables_half(L, m->d_pkovf, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(&over, m->d_pkovf, sizeof over, hipMemcpyDeviceToHost, s);
+  const hipError_t es = hipStreamSynchronize(s);  // also when a call above failed: `bases` may be in flight
+  if (e != hipSuccess) return hip_fail(e, "pack tables (fp16) launch");
+  if (es != hipSuccess) return hip_fail(es, "pack tables (fp16) synchronize");
+  if (over != 0) {
+    if (overflow_count) *overflow_count = (int64_t)(uint32_t)over;
+    return fail(DFWFM_ERR_UNSUPPORTED,
+                "pack_tables_half: %u categorical second-order values round to +-inf in fp16 (|x| >= 65520); the "
+                "model stays on the plain tables", (unsigned)over);
+  }
+  m->pkw = pkw;
+  m->pkh = 1;
+  m->pk_rows = rows;
+  *enabled = 1;
+  return DFWFM_OK;
+}
+
+int dfwfm_model_serving_copy_bytes(dfwfm_model* m, int64_t* bytes) {
+  if (!m || !bytes) return fail(DFWFM_ERR_INVALID_ARG, "null argument");
+  *bytes = m->pkw ? (int64_t)(m->pk_rows * (size_t)m->pkw * sizeof(float)) : 0;
   return DFWFM_OK;
 }
 
@@ -1520,6 +1606,7 @@ int dfwfm_train_forward(dfwfm_model* m, const int64_t* xi, int64_t xi_stride, co
   fill_forward_args(m, a, xi, xi_stride, xv, xv_stride, batch, out);
   a.pk = nullptr;  // the training forward reads the tables the optimizer updates, never the serving copy
   a.pkw = 0;
+  a.pkh = 0;
   a.flags |= kTrain | ((m->H > 0 && dropout_p > 0.f) ? kDrop : 0);
   a.sv_e = m->sv_e;
   a.sv_fo = m->sv_fo;

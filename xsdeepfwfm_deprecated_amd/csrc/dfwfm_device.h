@@ -115,6 +115,35 @@ __device__ __forceinline__ void load_row_fo(float (&v)[D], float& fo, const floa
   fo = x[D / 4][D % 4];
 }
 
+// one row of the fp16 serving copy (dfwfm_model_pack_tables_half): D halves of second order, padded to 4 bytes, then
+// the f32 first-order weight, from a 16-byte aligned row: ceil((2 D + 4) / 16) dwordx4 loads (two at D = 10, where
+// the f32 row takes three).  half -> float is exact.
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+template <int D>
+__device__ __forceinline__ void load_row_fo_h(float (&v)[D], float& fo, const float* __restrict__ src) {
+  constexpr int FO = half_row_fo_word(D);
+  constexpr int NQ = FO / 4 + 1;
+  u32x4 x[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) x[q] = reinterpret_cast<const u32x4*>(src)[q];
+#pragma unroll
+  for (int d = 0; d < D; ++d) {
+    const uint32_t w = x[d / 8][(d / 2) % 4];
+    v[d] = (float)__builtin_bit_cast(_Float16, (uint16_t)((d & 1) ? w >> 16 : w));
+  }
+  const uint32_t fw = x[FO / 4][FO % 4];  // (a copy: a bit cast of the vector element itself reads element 0)
+  fo = __builtin_bit_cast(float, fw);
+}
+
+// a row of whichever serving copy is in use (FwdArgs::pkh, wave-uniform)
+template <int D>
+__device__ __forceinline__ void load_row_pk(float (&v)[D], float& fo, const float* __restrict__ src, int pkh) {
+  if (pkh)
+    load_row_fo_h<D>(v, fo, src);
+  else
+    load_row_fo<D>(v, fo, src);
+}
+
 // row combine modes: 0 = a * scale (numerical / plain, scale 1), 1 = a * b (QR mult), 2 = a + b (QR add)
 __device__ __forceinline__ float combine(int mode, float a, float b, float scale) {
   return mode == 1 ? a * b : (mode == 2 ? a + b : a * scale);

@@ -171,9 +171,12 @@ __device__ __forceinline__ void k_loop_rt(f32x4 (&acc)[RT][TPW], const float* __
 }  // namespace
 
 // QR: some field may be a QR embedding (false: no second operand, row descriptors loaded directly with the keys)
-template <int D, bool QR>
+// HT: the serving copy is the fp16 one (dfwfm_model_pack_tables_half; QR = false only): a template parameter, so that
+// the instantiations the default path runs are the code they were
+template <int D, bool QR, bool HT = false>
 __global__ void __launch_bounds__(kNTH) __attribute__((amdgpu_waves_per_eu(4)))
 fwd32_kernel(FwdArgs p) {
+  static_assert(!HT || !QR, "the fp16 serving copy: never with QR fields");
   constexpr int RPT = (kRows * 48 + kNTH - 1) / kNTH;  // gather rows per thread: F <= 48
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x;
@@ -371,7 +374,10 @@ fwd32_kernel(FwdArgs p) {
         for (int d = 0; d < D; ++d) vb[k][d] = 0.f;
       }
       if (!QR && live[k] && pkrow[QR ? 0 : k]) {  // second and first order in one aligned row
-        load_row_fo<D>(va[k], fa[k], pa[k]);
+        if constexpr (HT)
+          load_row_fo_h<D>(va[k], fa[k], pa[k]);
+        else
+          load_row_fo<D>(va[k], fa[k], pa[k]);
       } else {
         if (live[k] && needE) {
           load_row<D>(va[k], pa[k]);
@@ -673,6 +679,7 @@ bool fwd32_supported(int F, int D, int H, int NT, int NC0, int tailI, int NG) {
 hipError_t launch_fwd32(const FwdArgs& a, int D, size_t lds, hipStream_t s) {
   if (D != 10) return hipErrorInvalidValue;
   auto k = (a.flags & kHasQR) ? fwd32_kernel<10, true> : fwd32_kernel<10, false>;
+  if (a.pkh) k = fwd32_kernel<10, false, true>;  // (the fp16 copy is never built for a model with QR fields)
   hipError_t e = ensure_lds_limit(reinterpret_cast<const void*>(k), lds);
   if (e != hipSuccess) return e;
   const unsigned grid = fwd_grid(a, kRows);

@@ -271,7 +271,7 @@ int8_fused_kernel(const FwdArgs p, const Int8Geo q) {
           for (int d = 0; d < D; ++d) vb[k][d] = 0.f;
         }
         if (live[k] && pkrow[k]) {
-          load_row_fo<D>(va[k], fa[k], pa[k]);
+          load_row_pk<D>(va[k], fa[k], pa[k], p.pkh);
         } else {
           if (live[k] && needE) {
             load_row<D>(va[k], pa[k]);

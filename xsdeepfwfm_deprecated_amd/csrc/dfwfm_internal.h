@@ -71,6 +71,7 @@ struct FwdArgs {
   int32_t* err;
   const float* const* pk;  // dfwfm_model_pack_tables: per field, rows of pkw floats (emb2 row, emb1 weight, zero
   int32_t pkw;             // pad) for the categorical fields; pkw = 0: the plain tables (PART 3 reads it)
+  int32_t pkh;             // 1: the fp16 copy of dfwfm_model_pack_tables_half (pkw is still the row stride in floats)
   const float* upack;  // FwFM A-operand fragments [MT][S][64]: strictly-upper (R + R^T)/2
   const int2* pairs;   // kPairs: the nonzero strictly-upper entries of (R + R^T)/2, (k | l << 16, w bits), k-major
   int32_t npairs;
@@ -588,6 +589,13 @@ struct PackTabList {
   int32_t nf, D, pkw;
 };
 hipError_t launch_pack_tables(const PackTabList& L, hipStream_t s);
+// dfwfm_model_pack_tables_half: the fp16 rows [D halves | pad to 4 B | f32 emb1 weight | zero pad]
+constexpr int half_row_fo_word(int D) { return (2 * D + 3) / 4; }  // the dword that holds the first-order weight
+constexpr int half_row_bytes(int D) {  // row stride: 32 B while the row fits, else the next multiple of 16 B
+  return 4 * half_row_fo_word(D) + 4 <= 32 ? 32 : (4 * half_row_fo_word(D) + 4 + 15) & ~15;
+}
+// L.pkw: the row stride in floats (half_row_bytes / 4); *overflow counts the values that round to +-inf
+hipError_t launch_pack_tables_half(const PackTabList& L, int32_t* overflow, hipStream_t s);
 // the gather + shallow part alone (-> a.part_e / a.part_fs): the sparse deep tower's first launch
 hipError_t launch_forward_gather(const FwdArgs& a, int D, size_t lds1, hipStream_t s);
 hipError_t launch_pack_list(const PackList& L, int total_blocks, hipStream_t s);

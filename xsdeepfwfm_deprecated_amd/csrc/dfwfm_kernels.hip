@@ -25,6 +25,7 @@
 //            and reduce through LDS; bias+ReLU fused into the epilogue,
 //            net_1_fc fused into the last layer's epilogue;
 //   combine  total = ((first + second) + deep) + bias   (:458 order).
+#include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -70,7 +71,9 @@ namespace dfwfm {
 // split tail tile rides on its register sets (mlp_k_loop_s)
 // QR: some field may be a QR embedding (false: the gather carries no second operand and loads its row descriptors
 // directly -- PART 3, and PART 0's static form)
-template <int D, int TPW, int KS, bool TRAIN, int PART, int NG, int NS, bool QR = true>
+// HT: the serving copy is the fp16 one (dfwfm_model_pack_tables_half; QR = false only).  A template parameter, not a
+// branch on p.pkh: the branch cost registers or scratch in a dozen instantiations (profiles/half_tables)
+template <int D, int TPW, int KS, bool TRAIN, int PART, int NG, int NS, bool QR = true, bool HT = false>
 __global__ void __launch_bounds__(64 * NG * KS)
 __attribute__((amdgpu_waves_per_eu(PART == 1 ? 3 : (PART == 3 ? (NG == 4 ? DFWFM_P3_WPE4 : DFWFM_P3_WPE)
                                                                : (NG == 8 ? (TRAIN ? 2 : 4) : DFWFM_FWD_WPE)))))
@@ -168,6 +171,7 @@ fwd_kernel(FwdArgs p) {
   // the inference forward with the serving copy (dfwfm_model_pack_tables): a categorical row and its first-order
   // weight are ONE row of pkw floats
   constexpr bool kPackable = (PART == 3 || (PART == 0 && !TRAIN)) && !QR && kDirectDesc;
+  static_assert(!HT || kPackable, "the fp16 serving copy: an instantiation that reads the serving copy");
   bool pkrow[kPackable ? RPT : 1];
   if constexpr (kDirectDesc) {
 #pragma unroll
@@ -337,7 +341,10 @@ fwd_kernel(FwdArgs p) {
         for (int d = 0; d < D; ++d) vb[k][d] = 0.f;
       }
       if (kPackable && live[k] && pkrow[kPackable ? k : 0]) {  // second and first order in one aligned row
-        load_row_fo<D>(va[k], fa[k], pa[k]);
+        if constexpr (HT)
+          load_row_fo_h<D>(va[k], fa[k], pa[k]);
+        else
+          load_row_fo<D>(va[k], fa[k], pa[k]);
       } else {
         if (live[k] && needE) {
           load_row<D>(va[k], pa[k]);
@@ -979,6 +986,14 @@ static hipError_t launch_fwd_t(const FwdArgs& a, size_t lds, hipStream_t s) {
   auto k = (S25 && a.ns == 25) ? ((S25D && !(a.flags & kHasQR)) ? fwd_kernel<D, TPW, KS, TRAIN, PART, NG, S25 ? 25 : 0, false>
                                                                : fwd_kernel<D, TPW, KS, TRAIN, PART, NG, S25 ? 25 : 0>)
                                : fwd_kernel<D, TPW, KS, TRAIN, PART, NG, 0>;
+  // the fp16 serving copy (a.pkh; never with QR fields): the forms that read it, static and generic
+  if constexpr (PART == 0 && !TRAIN && KS == 1 && DFWFM_DIRECT_DESC_DEEP) {
+    if (a.pkh)
+      k = (S25 && a.ns == 25) ? fwd_kernel<D, TPW, KS, false, 0, NG, S25 ? 25 : 0, false, true>
+                              : fwd_kernel<D, TPW, KS, false, 0, NG, 0, false, true>;
+  } else if (a.pkh) {
+    return hipErrorInvalidValue;  // this form would read the plain, unrounded tables
+  }
   {
     hipError_t e = ensure_lds_limit(reinterpret_cast<const void*>(k), lds);
     if (e != hipSuccess) return e;
@@ -1031,18 +1046,25 @@ static hipError_t launch_fwd_d(const FwdArgs& a, int tpw, int ks, int ng, size_t
     // batch sets (a.nb > 1): four waves -- with the CU slots refilled across batch boundaries, five four-wave
     // workgroups per CU beat three eight-wave ones (2.52 vs 2.92 us per batch, profiles/r03/r03be_*)
     const bool w8 = qr || (png ? png != 4 : a.nb <= 1);
-    auto pick = [&](auto ng_, auto qr_) {
+    auto pick = [&](auto ng_, auto qr_, auto ht_) {
       constexpr int NG = decltype(ng_)::value;
       constexpr bool Q = decltype(qr_)::value;
-      return a.MT == 1 ? fwd_kernel<D, 1, 1, false, 3, NG, 1, Q>
-           : a.MT == 2 ? fwd_kernel<D, 1, 1, false, 3, NG, 2, Q>
-           : a.MT == 3 ? fwd_kernel<D, 1, 1, false, 3, NG, 3, Q> : fwd_kernel<D, 1, 1, false, 3, NG, 4, Q>;
+      constexpr bool HT = decltype(ht_)::value;
+      return a.MT == 1 ? fwd_kernel<D, 1, 1, false, 3, NG, 1, Q, HT>
+           : a.MT == 2 ? fwd_kernel<D, 1, 1, false, 3, NG, 2, Q, HT>
+           : a.MT == 3 ? fwd_kernel<D, 1, 1, false, 3, NG, 3, Q, HT> : fwd_kernel<D, 1, 1, false, 3, NG, 4, Q, HT>;
     };
     using I4 = std::integral_constant<int, 4>;
     using I8 = std::integral_constant<int, 8>;
     using T = std::true_type;
     using Fl = std::false_type;
-    auto k = qr ? pick(I8{}, T{}) : (w8 ? pick(I8{}, Fl{}) : pick(I4{}, Fl{}));
+    auto k = qr ? pick(I8{}, T{}, Fl{}) : (w8 ? pick(I8{}, Fl{}, Fl{}) : pick(I4{}, Fl{}, Fl{}));
+    if (a.pkh) {  // the fp16 serving copy (never with QR fields)
+      if constexpr (DFWFM_P3_DIRECT_DESC)
+        k = w8 ? pick(I8{}, Fl{}, T{}) : pick(I4{}, Fl{}, T{});
+      else
+        return hipErrorInvalidValue;
+    }
     const int ng = w8 ? 8 : 4;
     const size_t lds3 = sizeof(float) * (size_t)lds_layout(a.F, D, a.MT, a.S, a.SX, a.SY, 1, 1, false, false, ng,
                                                             true, (a.flags & kFoFwlw) != 0).total;
@@ -1113,6 +1135,51 @@ __global__ void __launch_bounds__(256) pack_tables_kernel(const PackTabList L) {
 hipError_t launch_pack_tables(const PackTabList& L, hipStream_t s) {
   if (L.nf <= 0 || L.blk0[L.nf] <= 0) return hipSuccess;
   hipLaunchKernelGGL(pack_tables_kernel, dim3(L.blk0[L.nf]), dim3(256), 0, s, L);
+  return hipGetLastError();
+}
+
+// dfwfm_model_pack_tables_half: thread = one row of one categorical field, written as pkw / 4 16-byte stores:
+// [emb2 row as D halves, two per dword | zero half when D is odd | emb1 weight (f32) | zeros].  Each value is
+// rounded once, to nearest even, subnormals kept; the values that round to +-inf (|x| >= 65520) are counted.
+__global__ void __launch_bounds__(256) pack_tables_half_kernel(const PackTabList L, int32_t* overflow) {
+  int j = 0;
+  while (j + 1 < L.nf && (int)blockIdx.x >= L.blk0[j + 1]) ++j;  // this workgroup's field (wave-uniform)
+  const int64_t r = (int64_t)((int)blockIdx.x - L.blk0[j]) * 256 + threadIdx.x;
+  if (r >= L.n[j]) return;
+  const float* e2 = L.emb2[j] + r * L.D;
+  const float e1 = L.emb1[j][r];
+  const int fo = half_row_fo_word(L.D);
+  u32x4* dst = reinterpret_cast<u32x4*>(L.dst[j] + r * L.pkw);
+  int over = 0;
+  for (int q = 0; q < L.pkw / 4; ++q) {
+    u32x4 v;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int w = 4 * q + i;
+      uint32_t bits = 0;
+      if (w < fo) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int e = 2 * w + h;
+          if (e < L.D) {
+            const float x = e2[e];
+            over += fabsf(x) >= 65520.f;
+            bits |= (uint32_t)__half_as_ushort(__float2half_rn(x)) << (16 * h);
+          }
+        }
+      } else if (w == fo) {
+        bits = __float_as_uint(e1);
+      }
+      v[i] = bits;
+    }
+    dst[q] = v;
+  }
+  if (over) atomicAdd(overflow, over);
+}
+
+hipError_t launch_pack_tables_half(const PackTabList& L, int32_t* overflow, hipStream_t s) {
+  if (L.nf <= 0 || L.blk0[L.nf] <= 0) return hipSuccess;
+  hipLaunchKernelGGL(pack_tables_half_kernel, dim3(L.blk0[L.nf]), dim3(256), 0, s, L, overflow);
   return hipGetLastError();
 }
 

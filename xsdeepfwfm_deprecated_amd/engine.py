@@ -15,10 +15,13 @@ it in sync with a DeepFMs module's parameters.
 from __future__ import annotations
 
 import ctypes
+import logging
 
 import torch
 
 from . import _lib
+
+_log = logging.getLogger(__name__)
 
 
 def _ptr(t):
@@ -164,15 +167,52 @@ class ForwardEngine:
         weight in one aligned row) for the forward without a deep tower, rebuilt whenever a table tensor moved or
         changed (torch's version counters; the fused training step resets the key, its updates bypass them).
         tables: the categorical fields' (emb2, emb1) tensors.  Returns whether the copy is in use."""
-        key = (bool(enable),) + tuple((t.data_ptr(), t._version) for pair in tables for t in pair if t is not None)
+        return self._sync_packed(tables, enable, "f32")
+
+    def sync_packed_half(self, tables) -> bool:
+        """dfwfm_model_pack_tables_half (include/dfwfm_half_tables.h): the serving copy with the second-order rows in
+        fp16, rebuilt as sync_packed rebuilds the f32 one (the two share one allocation and one key, so changing the
+        dtype re-packs).  There is one fp16 path and no fallback: a model the copy does not cover, or a value that
+        rounds to +-inf, raises DfwfmError and leaves the engine on the plain tables."""
+        return self._sync_packed(tables, True, "fp16")
+
+    def _sync_packed(self, tables, enable, dtype):
+        key = (bool(enable), dtype) + tuple((t.data_ptr(), t._version) for pair in tables for t in pair
+                                            if t is not None)
         if key == getattr(self, "_packed_key", None):
             return self._packed_on
         en = ctypes.c_int32(0)
-        _lib.check(_lib.lib().dfwfm_model_pack_tables(self.handle, int(bool(enable)), ctypes.byref(en),
-                                                      _stream_handle(self.device)), "dfwfm_model_pack_tables")
+        self._packed_key = None
+        self._packed_on = False
+        if dtype == "fp16":
+            over = ctypes.c_int64(0)
+            rc = _lib.lib().dfwfm_model_pack_tables_half(self.handle, 1, ctypes.byref(en), ctypes.byref(over),
+                                                         _stream_handle(self.device))
+            if rc != _lib.DFWFM_OK and over.value:
+                raise _lib.DfwfmError(f"table_dtype='fp16': {over.value} categorical second-order value(s) round to "
+                                      "+-inf in fp16 (|x| >= 65520); the fp16 serving copy is not built")
+            _lib.check(rc, "dfwfm_model_pack_tables_half")
+            if not en.value:
+                raise _lib.DfwfmError("table_dtype='fp16': the serving copy does not cover this model (it needs a "
+                                      "second order, first-order tables and no QR field); its forward would read the "
+                                      "unrounded f32 tables")
+        else:
+            _lib.check(_lib.lib().dfwfm_model_pack_tables(self.handle, int(bool(enable)), ctypes.byref(en),
+                                                          _stream_handle(self.device)), "dfwfm_model_pack_tables")
         self._packed_on = bool(en.value)
         self._packed_key = key
+        nbytes = self.serving_copy_bytes()
+        if nbytes > getattr(self, "_copy_logged", 0):  # once per allocation: the copy only ever grows
+            self._copy_logged = nbytes
+            _log.info("serving copy of the categorical tables: %.1f MB (%s rows)", nbytes / 1e6, dtype)
         return self._packed_on
+
+    def serving_copy_bytes(self) -> int:
+        """dfwfm_model_serving_copy_bytes: the bytes of the serving copy in use (f32 or fp16), 0 on the plain tables."""
+        n = ctypes.c_int64(0)
+        _lib.check(_lib.lib().dfwfm_model_serving_copy_bytes(self.handle, ctypes.byref(n)),
+                   "dfwfm_model_serving_copy_bytes")
+        return int(n.value)
 
     def sync_pairs(self, max_pairs: int) -> bool:
         """(Re)build the pruned FwFM's nonzero pair list after a weight update (syncs the stream once per
