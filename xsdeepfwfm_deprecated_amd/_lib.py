@@ -38,7 +38,8 @@ def _units():
     for s in PER_D_SOURCES:
         u += [(s, f"{os.path.splitext(s)[0]}_d{d}.o", [f"-DDFWFM_KD={d}"]) for d in EMB_SIZES]
     return u
-HEADERS = ["dfwfm_internal.h", "dfwfm_device.h", "dfwfm_adam.h", os.path.join("..", "..", "include", "dfwfm.h"),
+HEADERS = ["dfwfm_internal.h", "dfwfm_device.h", "dfwfm_fused_stage.h", "dfwfm_adam.h",
+           os.path.join("..", "..", "include", "dfwfm.h"),
            os.path.join("..", "..", "include", "dfwfm_serve.h"), os.path.join("..", "..", "include", "dfwfm_bf16.h"),
            os.path.join("..", "..", "include", "dfwfm_bf16_fused.h"), os.path.join("..", "..", "include", "dfwfm_fold.h"),
            os.path.join("..", "..", "include", "dfwfm_bf16_fold.h"), os.path.join("..", "..", "include", "dfwfm_int8.h"),

@@ -6,7 +6,10 @@
 //
 //   stage 1  descriptors, keys, the gather of the f32 E tile into LDS, the table / fwlw first order and the FwFM /
 //            FM second order as U'E pieces -- the arithmetic of the gather launch (fwd_kernel PART 3 with
-//            kP3Pieces), per 16-row sub-tile, so first + second are the bits dfwfm_forward_gather writes;
+//            kP3Pieces), per 16-row sub-tile, so first + second are the bits dfwfm_forward_gather writes.  The
+//            gather and the first + second reduction are the stage_* functions of dfwfm_fused_stage.h, which the
+//            int8 forward (dfwfm_int8.hip) calls too; the staging and the shallow half stand in both kernel bodies
+//            (that header says why);
 //   stage 2  the hidden layers on v_mfma_f32_16x16x32_bf16: the weights are the A operand, 16-byte fragments of the
 //            pack of dfwfm_model_pack_bf16 streamed from L2 (wave w owns output tiles w, w + 8, ... for every row
 //            sub-tile, so a fragment feeds RT MFMAs), the activations the B operand, read from the LDS tile: layer 1
@@ -31,10 +34,14 @@
 // fragments of bf16_fold_pack_kernel (categorical columns of bf16(W1) | bf16(P) | zeros).  xsh + WE is a multiple of 8,
 // so SE = 4 mod 8 still.  The FwFM then clamps its padded fields to F (Xv lies where field F would).  Layers 2..H, the
 // shallow half and the unfolded forms are untouched.
+//
+// The workgroup shape (kF*), the stage-1 scratch, the weight fragment ring of the K loop, the last layer's share, the
+// logits and the launch are dfwfm_fused_stage.h's too.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "dfwfm_device.h"
+#include "dfwfm_fused_stage.h"
 #include "dfwfm_internal.h"
 
 namespace dfwfm {
@@ -42,16 +49,6 @@ namespace dfwfm {
 namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int kFW = 8;            // waves of a workgroup
-constexpr int kFTH = 64 * kFW;
-constexpr int kFTPW = 4;          // output tiles per wave: deep_nodes <= 8 * 4 * 16 = 512
-constexpr int kFMaxF = 48;        // fields: three FwFM row tiles, as the pieces form of the gather launch
-constexpr int kFMT = 3;
-constexpr int kFPD = 3;           // fragment sets in flight in the K loop
-constexpr size_t kFLdsMax = 160 * 1024;
 
 // two f32 to two bf16, round to nearest even, NaN kept: lo in bits 0-15
 __device__ __forceinline__ uint32_t cvt_pk_bf16(float lo, float hi) {
@@ -61,7 +58,8 @@ __device__ __forceinline__ uint32_t cvt_pk_bf16(float lo, float hi) {
 }
 
 struct FusedLds {
-  int tile, fs, desc, lw, fwlw, fo, part2, part, total;
+  int tile, fs, part, total;
+  StageLds st;
 };
 
 __host__ __device__ inline FusedLds fused_layout(int rows, int F, int D, int NT, int SE, int SB) {
@@ -70,12 +68,8 @@ __host__ __device__ inline FusedLds fused_layout(int rows, int F, int D, int NT,
   const int tf = rows * SE, tb = rows * SB / 2;
   L.tile = o;  o += r4(tf > tb ? tf : tb);
   L.fs = o;    o += rows;
-  int s = o;
-  L.desc = s;  s += r4(14 * F);
-  L.lw = s;    s += r4(F);
-  L.fwlw = s;  s += r4(F * D);
-  L.fo = s;    s += rows * r4(F);
-  L.part2 = s; s += rows * D;  // per 16-row sub-tile, its 16 D column sums
+  L.st = stage_layout(o, rows, F, D);
+  const int s = L.st.end;
   int t = o;
   L.part = t;  t += rows * NT;
   L.total = r4(s > t ? s : t);
@@ -98,20 +92,14 @@ __device__ __forceinline__ u32x4 act_frag(const char* p) {
 
 // one layer's K loop of one wave: its kFTPW output tiles (wt[j]: the tile's fragments of K step 0) times the RT row
 // sub-tiles (brow: this lane's 16 bytes of K step 0 in sub-tile 0; rt_bytes / c_bytes to the next sub-tile / K step).
-// kFPD weight fragment sets in a ring, each loaded kFPD - 1 steps ahead of its MFMAs (the L2 round trip); unrolled by
-// kFPD so no set is copied.  The activation fragments come from LDS in their own step: the other waves of the SIMD
-// cover that latency, and a ring of them cost the 32-row form its second workgroup per CU (registers).
+// The weight fragment sets go through the ring of ring_k_loop.  The activation fragments come from LDS in their own
+// step: the other waves of the SIMD cover that latency, and a ring of them cost the 32-row form its second workgroup
+// per CU (registers).
 template <int RT, bool F32IN>
 __device__ __forceinline__ void fused_k_loop(f32x4 (&acc)[RT][kFTPW], const u32x4* const (&wt)[kFTPW], int lane,
                                              const char* brow, int rt_bytes, int KC) {
-  constexpr int PD = RT == 1 ? kFPD : kFPD - 1;  // 32 and 64 rows: twice / four times the accumulators, one set fewer
   constexpr int c_bytes = F32IN ? 128 : 64;
-  u32x4 wf[PD][kFTPW];
-  auto load = [&](int c, u32x4(&wq)[kFTPW]) {
-#pragma unroll
-    for (int j = 0; j < kFTPW; ++j) wq[j] = (wt[j] + c * 64)[lane];  // a wave-uniform base, the lane as the offset
-  };
-  auto mma = [&](int c, const u32x4(&wq)[kFTPW]) {
+  ring_k_loop<ring_depth(RT), kFTPW>(wt, lane, KC, [&](int c, const u32x4(&wq)[kFTPW]) {
     u32x4 aq[RT];
 #pragma unroll
     for (int i = 0; i < RT; ++i) aq[i] = act_frag<F32IN>(brow + i * rt_bytes + c * c_bytes);
@@ -122,27 +110,7 @@ __device__ __forceinline__ void fused_k_loop(f32x4 (&acc)[RT][kFTPW], const u32x
       for (int j = 0; j < kFTPW; ++j)
         acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wq[j]), x, acc[i][j], 0, 0, 0);
     }
-  };
-#pragma unroll
-  for (int p = 0; p < PD - 1; ++p)
-    if (p < KC) load(p, wf[p]);
-  int c = 0;
-  for (; c + 2 * PD - 1 <= KC; c += PD) {  // steady state: every step's refill is in range
-#pragma unroll
-    for (int p = 0; p < PD; ++p) {
-      load(c + p + PD - 1, wf[(p + PD - 1) % PD]);
-      mma(c + p, wf[p]);
-    }
-  }
-  for (; c < KC; c += PD) {  // the last 1 .. 2 PD - 2 steps (conditions wave-uniform)
-#pragma unroll
-    for (int p = 0; p < PD; ++p) {
-      if (c + p < KC) {
-        if (c + p + PD - 1 < KC) load(c + p + PD - 1, wf[(p + PD - 1) % PD]);
-        mma(c + p, wf[p]);
-      }
-    }
-  }
+  });
 }
 
 // RT: 16-row sub-tiles per workgroup; QR: some field may be a QR embedding (false: the gather carries no second
@@ -154,15 +122,12 @@ bf16_fused_kernel(const FwdArgs p, const Bf16FusedGeo q) {
   constexpr int D = 10;
   constexpr int ROWS = 16 * RT;
   constexpr int LR = RT == 1 ? 4 : (RT == 2 ? 5 : 6);  // log2(ROWS)
-  constexpr int RPT = RT == 1 ? 2 : 3;                  // gather rows per thread and pass
-  constexpr int NPASS = (ROWS * kFMaxF + kFTH * RPT - 1) / (kFTH * RPT);
   static_assert(RT == 1 || RT == 2 || RT == 4, "16, 32 or 64 rows");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int F = p.F;
-  const int num = p.num;
   const int flags = p.flags;
   const int Fp = r4(F);
   const int SE = q.SE, SB = q.SB;
@@ -171,21 +136,16 @@ bf16_fused_kernel(const FwdArgs p, const Bf16FusedGeo q) {
   float* etile = smem + L.tile + xsh;  // (the folded layer 1: the categorical block 16-byte aligned)
   uint16_t* atile = reinterpret_cast<uint16_t*>(smem + L.tile);
   float* fs = smem + L.fs;
-  FieldDev* desc = reinterpret_cast<FieldDev*>(smem + L.desc);
-  float* lw_s = smem + L.lw;
-  float* fwlw_s = smem + L.fwlw;
-  float* fo = smem + L.fo;
-  float* part2 = smem + L.part2;
+  const StageScratch sc = stage_scratch(smem, L.st);
   float* part = smem + L.part;
   const TileRef tr = tile_ref<ROWS>(p);  // batch set: this workgroup's batch
-  const int64_t b0 = tr.b0;
 
-  // ---- stage 1: descriptors and shallow parameters to LDS, the E tile's zero padding -----------------------------
+  // ---- stage 1: descriptors and shallow parameters to LDS, the E tile's zero padding; then dfwfm_fused_stage.h ------
   for (int i = tid; i < 7 * F; i += kFTH)
-    reinterpret_cast<u32x2*>(desc)[i] = reinterpret_cast<const u32x2*>(p.fields)[i];
+    reinterpret_cast<u32x2*>(sc.desc)[i] = reinterpret_cast<const u32x2*>(p.fields)[i];
   if (flags & kFoFwlw)
-    for (int i = tid; i < F * D; i += kFTH) fwlw_s[i] = p.fwlw[i];
-  if ((flags & kFoLw) && tid < F) lw_s[tid] = p.lw[tid];
+    for (int i = tid; i < F * D; i += kFTH) sc.fwlw[i] = p.fwlw[i];
+  if ((flags & kFoLw) && tid < F) sc.lw[tid] = p.lw[tid];
   {
     // columns [F D, WE): layer 1 reads K steps of 32 up to k0 + KC0 * 32, the FwFM fields up to 4 S (the folded
     // layer 1's Xv columns are among them: the gather's numerical rows write them after the barrier)
@@ -197,134 +157,19 @@ bf16_fused_kernel(const FwdArgs p, const Bf16FusedGeo q) {
     }
   }
   __syncthreads();
-
-  // ---- the gather: E rows and the table first order, RPT rows per thread and pass ------------------------------------
-  {
-    const bool needE = (flags & kNeedE) != 0;
-    const bool fo_tab = (flags & kFoTables) != 0;
-    constexpr int RQ = QR ? RPT : 1;
-#pragma unroll 1
-    for (int pass = 0; pass < NPASS; ++pass) {
-      const float* pa[RPT];
-      const float* pb[RQ];
-      const float* qa[RPT];
-      const float* qb[RQ];
-      float scale[RPT];
-      int mode[RPT];
-      bool live[RPT], pkrow[RPT];
-      int64_t key[RPT];  // gather row r -> field f = r / ROWS, sample b = r % ROWS: index or Xv bits
-#pragma unroll
-      for (int k = 0; k < RPT; ++k) {
-        const int r = tid + (pass * RPT + k) * kFTH;
-        const int f = r >> LR;
-        const int64_t gb = b0 + (r & (ROWS - 1));
-        live[k] = f < F && gb < p.batch;
-        key[k] = 0;
-        if (live[k]) {
-          if (f < num)
-            key[k] = __float_as_int(tr.xv[gb * p.xv_stride + f]);
-          else
-            key[k] = tr.xi[gb * p.xi_stride + (f - num)];
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < RPT; ++k) {
-        const int r = tid + (pass * RPT + k) * kFTH;
-        const int f = r >> LR;
-        pa[k] = qa[k] = nullptr;
-        if constexpr (QR) pb[k] = qb[k] = nullptr;
-        scale[k] = 1.f;
-        mode[k] = 0;
-        pkrow[k] = false;
-        if (!live[k]) continue;
-        const FieldDev fd = desc[f];
-        if (f < num) {
-          scale[k] = __int_as_float((int)key[k]);
-          pa[k] = fd.emb2;
-          qa[k] = fd.emb1;
-        } else {
-          int64_t idx = key[k];
-          if (idx < 0 || idx >= fd.n) {
-            atomicOr(p.err, DFWFM_FLAG_INDEX_OUT_OF_RANGE);
-            idx = 0;
-          }
-          if (!QR && p.pkw != 0) {  // the serving copy: second and first order in one aligned row
-            pkrow[k] = true;
-            pa[k] = p.pk[f] + idx * p.pkw;
-          } else if (!QR || fd.c == 0) {
-            pa[k] = fd.emb2 + idx * D;
-            if (fo_tab) qa[k] = fd.emb1 + idx;
-          } else if constexpr (QR) {
-            const int64_t qq = idx / fd.c;
-            const int64_t rr = idx - qq * fd.c;
-            mode[k] = fd.op == 0 ? 1 : 2;
-            pa[k] = fd.emb2 + qq * D;
-            pb[k] = fd.emb2_r + rr * D;
-            if (fo_tab) {
-              qa[k] = fd.emb1 + qq;
-              qb[k] = fd.emb1_r + rr;
-            }
-          }
-        }
-      }
-      float va[RPT][D], vb[RQ][D], fa[RPT], fb[RQ];
-#pragma unroll
-      for (int k = 0; k < RPT; ++k) {
-        fa[k] = 0.f;
-#pragma unroll
-        for (int d = 0; d < D; ++d) va[k][d] = 0.f;
-        if constexpr (QR) {
-          fb[k] = 0.f;
-#pragma unroll
-          for (int d = 0; d < D; ++d) vb[k][d] = 0.f;
-        }
-        if (live[k] && pkrow[k]) {
-          load_row_pk<D>(va[k], fa[k], pa[k], p.pkh);
-        } else {
-          if (live[k] && needE) {
-            load_row<D>(va[k], pa[k]);
-            if constexpr (QR)
-              if (mode[k] != 0) load_row<D>(vb[k], pb[k]);
-          }
-          if (live[k] && fo_tab) {
-            fa[k] = *qa[k];
-            if constexpr (QR)
-              if (mode[k] != 0) fb[k] = *qb[k];
-          }
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < RPT; ++k) {
-        const int r = tid + (pass * RPT + k) * kFTH;
-        const int f = r >> LR;
-        const int b = r & (ROWS - 1);
-        if (f < F) {
-          if (needE) {
-            float e[D];
-#pragma unroll
-            for (int d = 0; d < D; ++d)
-              e[d] = live[k] ? combine(mode[k], va[k][d], QR ? vb[QR ? k : 0][d] : 0.f, scale[k]) : 0.f;
-            store_row<D>(etile + b * SE + f * D, e);
-            if (FOLD && f < nxv) etile[b * SE + F * D + f] = live[k] ? scale[k] : 0.f;  // the folded layer 1's K row
-          }
-          fo[b * Fp + f] = live[k] ? combine(mode[k], fa[k], QR ? fb[QR ? k : 0] : 0.f, scale[k]) : 0.f;
-        }
-      }
-    }
-  }
+  stage_gather<RT, QR, FOLD>(p, tr, sc, etile, SE, nxv, tid);
   __syncthreads();
-
   // ---- the shallow half: the expressions of fwd_kernel PART 3 (pieces form), per 16-row sub-tile ---------------------
   if (flags & kFoFwlw) {
     for (int r = tid; r < ROWS * F; r += kFTH) {
       const int f = r >> LR;
       const int b = r & (ROWS - 1);
       const float* e = etile + b * SE + f * D;
-      const float* w = fwlw_s + f * D;
+      const float* w = sc.fwlw + f * D;
       float s = 0.f;
 #pragma unroll
       for (int d = 0; d < D; ++d) s += e[d] * w[d];
-      fo[b * Fp + f] = s;
+      sc.fo[b * Fp + f] = s;
     }
   }
   if (flags & kHasSecond) {
@@ -379,33 +224,11 @@ bf16_fused_kernel(const FwdArgs p, const Bf16FusedGeo q) {
       }
       colv += __shfl_xor(colv, 16);
       colv += __shfl_xor(colv, 32);
-      if (lane < 16) part2[rt * 16 * D + n] = colv;  // column n's sum over k (row tiles in order)
+      if (lane < 16) sc.part2[rt * 16 * D + n] = colv;  // column n's sum over k (row tiles in order)
     }
   }
   __syncthreads();
-  // first[b] (lw projection or plain sum over fields) and second[b] (sum over d): 16 lanes per sample each take
-  // every 16th term, then a 16-lane DPP sum
-  for (int g4 = wave; g4 * 4 < ROWS; g4 += kFW) {
-    const int b = g4 * 4 + (lane >> 4);
-    const int qd = lane & 15;
-    float first = 0.f, second = 0.f;
-    for (int f0 = 0; f0 < F; f0 += 64) {
-      float x[4], l[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int f = min(f0 + 16 * k + qd, F - 1);
-        x[k] = fo[b * Fp + f];
-        l[k] = (flags & kFoLw) ? lw_s[f] : 1.f;
-      }
-#pragma unroll
-      for (int k = 0; k < 4; ++k) first = f0 + 16 * k + qd < F ? fmaf(x[k], l[k], first) : first;
-    }
-    if (flags & kHasSecond)
-      for (int d = qd; d < D; d += 16) second += part2[b * D + d];  // the sample's column sums
-    first = sum16(first);
-    second = sum16(second);
-    if (qd == 0) fs[b] = first + second;
-  }
+  stage_fs<RT>(p, sc, fs, lane, wave);
 
   // ---- stages 2 and 3: the hidden layers; the tile is read by every wave's K loop, then overwritten in place ----------
   const int rl = lane & 15, kq = lane >> 4;
@@ -463,14 +286,7 @@ bf16_fused_kernel(const FwdArgs p, const Bf16FusedGeo q) {
         if (!last) {
           *reinterpret_cast<u32x2*>(atile + row * SB + n0) = u32x2{cvt_pk_bf16(v[0], v[1]), cvt_pk_bf16(v[2], v[3])};
         } else {  // uniform: every lane takes part in the shuffles
-          float d = 0.f;
-          d = fmaf(v[0], fq[0], d);
-          d = fmaf(v[1], fq[1], d);
-          d = fmaf(v[2], fq[2], d);
-          d = fmaf(v[3], fq[3], d);
-          d += __shfl_xor(d, 16);
-          d += __shfl_xor(d, 32);
-          if (lv < 16) part[row * NT + t] = d;
+          last_layer_share(v, fq, lv, part + row * NT + t);
         }
       }
     }
@@ -482,12 +298,7 @@ bf16_fused_kernel(const FwdArgs p, const Bf16FusedGeo q) {
   }
 
   // ---- stage 4: logit[b] = (first_second[b] + the shares in tile order) + bias -----------------------------------------
-  if (tid < ROWS && b0 + tid < p.batch) {
-    const float* pp = part + tid * NT;
-    float deep = pp[0];
-    for (int t = 1; t < NT; ++t) deep += pp[t];
-    tr.out[b0 + tid] = (fs[tid] + deep) + p.bias[0];
-  }
+  stage_logits<ROWS>(p, tr, part, fs, NT, tid);
 }
 
 // dfwfm_model_fold_bf16: layer 1's fragments in the order of dfwfm_model_pack_bf16 over the folded K rows, one thread
@@ -532,10 +343,7 @@ template <int RT>
 hipError_t launch_rt(const FwdArgs& a, const Bf16FusedGeo& g, size_t lds, hipStream_t s) {
   auto k = g.nxv ? ((a.flags & kHasQR) ? bf16_fused_kernel<RT, true, true> : bf16_fused_kernel<RT, false, true>)
                  : ((a.flags & kHasQR) ? bf16_fused_kernel<RT, true, false> : bf16_fused_kernel<RT, false, false>);
-  const hipError_t e = ensure_lds_limit(reinterpret_cast<const void*>(k), lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k, dim3(fwd_grid(a, 16 * RT)), dim3(kFTH), lds, s, a, g);
-  return hipGetLastError();
+  return launch_fused_kernel(k, a, g, 16 * RT, kFTH, lds, s);
 }
 
 inline int kc_of(int cols16) { return (cols16 * 16 + 31) / 32; }

@@ -4,7 +4,9 @@
 // batch (RT = 1, 2) and carries them from Xi / Xv to the logits:
 //
 //   stage 1  descriptors, keys, the gather of the f32 E tile into LDS, the table / fwlw first order and the FwFM / FM
-//            second order as U'E pieces: a copy of the fused bf16 kernel's stage 1 (its unfolded form), the same bits;
+//            second order as U'E pieces, the fused bf16 kernel's stage 1 in its unfolded form and the same bits: the
+//            gather and the first + second reduction are the stage_* functions of dfwfm_fused_stage.h that it calls
+//            too, the staging and the shallow half its text again in this kernel's body (that header says why);
 //   stage 2  the f32 E rows quantized into the int8 tile: TPR = 512 / ROWS lanes of one wave per row hold the row's
 //            float4s in registers, take the row's max (NaN kept) by a shuffle tree, form inv = 127 / a and sx = a / 127
 //            (one division each) and write four int8 per dword; sx stays in LDS;
@@ -28,10 +30,14 @@
 // there, and an integer product with 0 is 0.
 // Rows past the batch hold zeros and run through every stage (every wave reaches every barrier); nothing of them is
 // written out.
+//
+// The workgroup shape (kF*), the stage-1 scratch, the weight fragment ring of the K loop, the last layer's share, the
+// logits and the launch are dfwfm_fused_stage.h's too.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "dfwfm_device.h"
+#include "dfwfm_fused_stage.h"
 #include "dfwfm_internal.h"
 
 namespace dfwfm {
@@ -39,16 +45,6 @@ namespace dfwfm {
 namespace {
 
 typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int kQW = 8;            // waves of a workgroup
-constexpr int kQTH = 64 * kQW;
-constexpr int kQTPW = 4;          // output tiles per wave: deep_nodes <= 8 * 4 * 16 = 512
-constexpr int kQMaxF = 48;        // fields: three FwFM row tiles
-constexpr int kQMT = 3;
-constexpr int kQPD = 3;           // fragment sets in flight in the K loop
-constexpr size_t kQLdsMax = 160 * 1024;
 
 // max that keeps a NaN of either side
 __device__ __forceinline__ float nanmax(float a, float b) { return (b != b || b > a) ? b : a; }
@@ -66,7 +62,8 @@ __device__ __forceinline__ uint32_t quant4(float x0, float x1, float x2, float x
 }
 
 struct Int8Lds {
-  int tile, qt, fs, sx, wmax, desc, lw, fwlw, fo, part2, part, total;
+  int tile, qt, fs, sx, wmax, part, total;
+  StageLds st;
 };
 
 __host__ __device__ inline Int8Lds int8_layout(int rows, int F, int D, int NT, int SE, int SQ) {
@@ -76,33 +73,23 @@ __host__ __device__ inline Int8Lds int8_layout(int rows, int F, int D, int NT, i
   L.qt = o;    o += rows * SQ / 4;
   L.fs = o;    o += rows;
   L.sx = o;    o += rows;
-  L.wmax = o;  o += rows * kQW;
-  int s = o;
-  L.desc = s;  s += r4(14 * F);
-  L.lw = s;    s += r4(F);
-  L.fwlw = s;  s += r4(F * D);
-  L.fo = s;    s += rows * r4(F);
-  L.part2 = s; s += rows * D;  // per 16-row sub-tile, its 16 D column sums
+  L.wmax = o;  o += rows * kFW;
+  L.st = stage_layout(o, rows, F, D);
+  const int s = L.st.end;
   int t = o;
   L.part = t;  t += rows * NT;
   L.total = r4(s > t ? s : t);
   return L;
 }
 
-// one layer's K loop of one wave: its kQTPW output tiles (wt[j]: the tile's fragments of K step 0) times the RT row
+// one layer's K loop of one wave: its kFTPW output tiles (wt[j]: the tile's fragments of K step 0) times the RT row
 // sub-tiles (brow: this lane's 16 bytes of K step 0 in sub-tile 0; rt_bytes to the next sub-tile, 64 bytes to the next
-// K step).  The weight fragment sets in a ring, each loaded PD - 1 steps ahead of its MFMAs (the L2 round trip),
-// unrolled by PD so no set is copied: fused_k_loop of the fused bf16 kernel on the int8 instruction.
+// K step).  The weight fragment sets go through the ring of ring_k_loop; the activation fragments come from LDS in their
+// own step, as in fused_k_loop of the fused bf16 kernel: the same loop on the int8 instruction.
 template <int RT>
-__device__ __forceinline__ void int8_k_loop(i32x4 (&acc)[RT][kQTPW], const u32x4* const (&wt)[kQTPW], int lane,
+__device__ __forceinline__ void int8_k_loop(i32x4 (&acc)[RT][kFTPW], const u32x4* const (&wt)[kFTPW], int lane,
                                             const char* brow, int rt_bytes, int KC) {
-  constexpr int PD = RT == 1 ? kQPD : kQPD - 1;
-  u32x4 wf[PD][kQTPW];
-  auto load = [&](int c, u32x4(&wq)[kQTPW]) {
-#pragma unroll
-    for (int j = 0; j < kQTPW; ++j) wq[j] = (wt[j] + c * 64)[lane];  // a wave-uniform base, the lane as the offset
-  };
-  auto mma = [&](int c, const u32x4(&wq)[kQTPW]) {
+  ring_k_loop<ring_depth(RT), kFTPW>(wt, lane, KC, [&](int c, const u32x4(&wq)[kFTPW]) {
     u32x4 aq[RT];
 #pragma unroll
     for (int i = 0; i < RT; ++i) aq[i] = *reinterpret_cast<const u32x4*>(brow + i * rt_bytes + c * 64);
@@ -110,50 +97,27 @@ __device__ __forceinline__ void int8_k_loop(i32x4 (&acc)[RT][kQTPW], const u32x4
     for (int i = 0; i < RT; ++i) {
       const i32x4 x = __builtin_bit_cast(i32x4, aq[i]);
 #pragma unroll
-      for (int j = 0; j < kQTPW; ++j)
+      for (int j = 0; j < kFTPW; ++j)
         acc[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, wq[j]), x, acc[i][j], 0, 0, 0);
     }
-  };
-#pragma unroll
-  for (int p = 0; p < PD - 1; ++p)
-    if (p < KC) load(p, wf[p]);
-  int c = 0;
-  for (; c + 2 * PD - 1 <= KC; c += PD) {  // steady state: every step's refill is in range
-#pragma unroll
-    for (int p = 0; p < PD; ++p) {
-      load(c + p + PD - 1, wf[(p + PD - 1) % PD]);
-      mma(c + p, wf[p]);
-    }
-  }
-  for (; c < KC; c += PD) {  // the last 1 .. 2 PD - 2 steps (conditions wave-uniform)
-#pragma unroll
-    for (int p = 0; p < PD; ++p) {
-      if (c + p < KC) {
-        if (c + p + PD - 1 < KC) load(c + p + PD - 1, wf[(p + PD - 1) % PD]);
-        mma(c + p, wf[p]);
-      }
-    }
-  }
+  });
 }
 
 // RT: 16-row sub-tiles per workgroup; QR: some field may be a QR embedding (false: the gather carries no second operand)
 template <int RT, bool QR>
-__global__ void __launch_bounds__(kQTH) __attribute__((amdgpu_waves_per_eu(4)))
+__global__ void __launch_bounds__(kFTH) __attribute__((amdgpu_waves_per_eu(4)))
 int8_fused_kernel(const FwdArgs p, const Int8Geo q) {
   constexpr int D = 10;
   constexpr int ROWS = 16 * RT;
   constexpr int LR = RT == 1 ? 4 : 5;   // log2(ROWS)
-  constexpr int RPT = RT == 1 ? 2 : 3;  // gather rows per thread and pass
-  constexpr int NPASS = (ROWS * kQMaxF + kQTH * RPT - 1) / (kQTH * RPT);
-  constexpr int TPR = kQTH / ROWS;      // lanes per row in the quantize pass: 32 or 16, inside one wave
-  constexpr int Q4 = (kQMaxF * D / 4 + TPR - 1) / TPR;  // float4s per lane: layer 1's K <= 480
+  constexpr int TPR = kFTH / ROWS;      // lanes per row in the quantize pass: 32 or 16, inside one wave
+  constexpr int Q4 = (kFMaxF * D / 4 + TPR - 1) / TPR;  // float4s per lane: layer 1's K <= 480
   static_assert(RT == 1 || RT == 2, "16 or 32 rows");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int F = p.F;
-  const int num = p.num;
   const int flags = p.flags;
   const int Fp = r4(F);
   const int SE = q.SE, SQ = q.SQ;
@@ -163,184 +127,66 @@ int8_fused_kernel(const FwdArgs p, const Int8Geo q) {
   float* fs = smem + L.fs;
   float* sx_s = smem + L.sx;
   float* wmax = smem + L.wmax;
-  FieldDev* desc = reinterpret_cast<FieldDev*>(smem + L.desc);
-  float* lw_s = smem + L.lw;
-  float* fwlw_s = smem + L.fwlw;
-  float* fo = smem + L.fo;
-  float* part2 = smem + L.part2;
+  const StageScratch sc = stage_scratch(smem, L.st);
   float* part = smem + L.part;
   const TileRef tr = tile_ref<ROWS>(p);  // batch set: this workgroup's batch
-  const int64_t b0 = tr.b0;
 
-  // ---- stage 1: descriptors and shallow parameters to LDS, the E tile's zero padding, the int8 tile zeroed -----------
-  for (int i = tid; i < 7 * F; i += kQTH)
-    reinterpret_cast<u32x2*>(desc)[i] = reinterpret_cast<const u32x2*>(p.fields)[i];
+  // ---- stage 1: descriptors and shallow parameters to LDS, the E tile's zero padding, the int8 tile zeroed; then
+  // dfwfm_fused_stage.h -------------------------------------------------------------------------------------------------
+  for (int i = tid; i < 7 * F; i += kFTH)
+    reinterpret_cast<u32x2*>(sc.desc)[i] = reinterpret_cast<const u32x2*>(p.fields)[i];
   if (flags & kFoFwlw)
-    for (int i = tid; i < F * D; i += kQTH) fwlw_s[i] = p.fwlw[i];
-  if ((flags & kFoLw) && tid < F) lw_s[tid] = p.lw[tid];
+    for (int i = tid; i < F * D; i += kFTH) sc.fwlw[i] = p.fwlw[i];
+  if ((flags & kFoLw) && tid < F) sc.lw[tid] = p.lw[tid];
   {
     // columns [F D, WE): the quantize pass reads float4s up to r4(F D), the FwFM fields up to 4 S
     const int zc = F * D;
     const int w = q.WE - zc;
-    for (int i = tid; i < ROWS * w; i += kQTH) {
+    for (int i = tid; i < ROWS * w; i += kFTH) {
       const int b = i / w;
       etile[b * SE + zc + (i - b * w)] = 0.f;
     }
-    for (int i = tid; i < ROWS * SQ / 16; i += kQTH) reinterpret_cast<u32x4*>(qtile)[i] = u32x4{0u, 0u, 0u, 0u};
+    for (int i = tid; i < ROWS * SQ / 16; i += kFTH) reinterpret_cast<u32x4*>(qtile)[i] = u32x4{0u, 0u, 0u, 0u};
   }
   __syncthreads();
-
-  // ---- the gather: E rows and the table first order, RPT rows per thread and pass ------------------------------------
-  {
-    const bool needE = (flags & kNeedE) != 0;
-    const bool fo_tab = (flags & kFoTables) != 0;
-    constexpr int RQ = QR ? RPT : 1;
-#pragma unroll 1
-    for (int pass = 0; pass < NPASS; ++pass) {
-      const float* pa[RPT];
-      const float* pb[RQ];
-      const float* qa[RPT];
-      const float* qb[RQ];
-      float scale[RPT];
-      int mode[RPT];
-      bool live[RPT], pkrow[RPT];
-      int64_t key[RPT];  // gather row r -> field f = r / ROWS, sample b = r % ROWS: index or Xv bits
-#pragma unroll
-      for (int k = 0; k < RPT; ++k) {
-        const int r = tid + (pass * RPT + k) * kQTH;
-        const int f = r >> LR;
-        const int64_t gb = b0 + (r & (ROWS - 1));
-        live[k] = f < F && gb < p.batch;
-        key[k] = 0;
-        if (live[k]) {
-          if (f < num)
-            key[k] = __float_as_int(tr.xv[gb * p.xv_stride + f]);
-          else
-            key[k] = tr.xi[gb * p.xi_stride + (f - num)];
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < RPT; ++k) {
-        const int r = tid + (pass * RPT + k) * kQTH;
-        const int f = r >> LR;
-        pa[k] = qa[k] = nullptr;
-        if constexpr (QR) pb[k] = qb[k] = nullptr;
-        scale[k] = 1.f;
-        mode[k] = 0;
-        pkrow[k] = false;
-        if (!live[k]) continue;
-        const FieldDev fd = desc[f];
-        if (f < num) {
-          scale[k] = __int_as_float((int)key[k]);
-          pa[k] = fd.emb2;
-          qa[k] = fd.emb1;
-        } else {
-          int64_t idx = key[k];
-          if (idx < 0 || idx >= fd.n) {
-            atomicOr(p.err, DFWFM_FLAG_INDEX_OUT_OF_RANGE);
-            idx = 0;
-          }
-          if (!QR && p.pkw != 0) {  // the serving copy: second and first order in one aligned row
-            pkrow[k] = true;
-            pa[k] = p.pk[f] + idx * p.pkw;
-          } else if (!QR || fd.c == 0) {
-            pa[k] = fd.emb2 + idx * D;
-            if (fo_tab) qa[k] = fd.emb1 + idx;
-          } else if constexpr (QR) {
-            const int64_t qq = idx / fd.c;
-            const int64_t rr = idx - qq * fd.c;
-            mode[k] = fd.op == 0 ? 1 : 2;
-            pa[k] = fd.emb2 + qq * D;
-            pb[k] = fd.emb2_r + rr * D;
-            if (fo_tab) {
-              qa[k] = fd.emb1 + qq;
-              qb[k] = fd.emb1_r + rr;
-            }
-          }
-        }
-      }
-      float va[RPT][D], vb[RQ][D], fa[RPT], fb[RQ];
-#pragma unroll
-      for (int k = 0; k < RPT; ++k) {
-        fa[k] = 0.f;
-#pragma unroll
-        for (int d = 0; d < D; ++d) va[k][d] = 0.f;
-        if constexpr (QR) {
-          fb[k] = 0.f;
-#pragma unroll
-          for (int d = 0; d < D; ++d) vb[k][d] = 0.f;
-        }
-        if (live[k] && pkrow[k]) {
-          load_row_pk<D>(va[k], fa[k], pa[k], p.pkh);
-        } else {
-          if (live[k] && needE) {
-            load_row<D>(va[k], pa[k]);
-            if constexpr (QR)
-              if (mode[k] != 0) load_row<D>(vb[k], pb[k]);
-          }
-          if (live[k] && fo_tab) {
-            fa[k] = *qa[k];
-            if constexpr (QR)
-              if (mode[k] != 0) fb[k] = *qb[k];
-          }
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < RPT; ++k) {
-        const int r = tid + (pass * RPT + k) * kQTH;
-        const int f = r >> LR;
-        const int b = r & (ROWS - 1);
-        if (f < F) {
-          if (needE) {
-            float e[D];
-#pragma unroll
-            for (int d = 0; d < D; ++d)
-              e[d] = live[k] ? combine(mode[k], va[k][d], QR ? vb[QR ? k : 0][d] : 0.f, scale[k]) : 0.f;
-            store_row<D>(etile + b * SE + f * D, e);
-          }
-          fo[b * Fp + f] = live[k] ? combine(mode[k], fa[k], QR ? fb[QR ? k : 0] : 0.f, scale[k]) : 0.f;
-        }
-      }
-    }
-  }
+  stage_gather<RT, QR, false>(p, tr, sc, etile, SE, 0, tid);
   __syncthreads();
-
   // ---- the shallow half: the expressions of fwd_kernel PART 3 (pieces form), per 16-row sub-tile ---------------------
   if (flags & kFoFwlw) {
-    for (int r = tid; r < ROWS * F; r += kQTH) {
+    for (int r = tid; r < ROWS * F; r += kFTH) {
       const int f = r >> LR;
       const int b = r & (ROWS - 1);
       const float* e = etile + b * SE + f * D;
-      const float* w = fwlw_s + f * D;
+      const float* w = sc.fwlw + f * D;
       float s = 0.f;
 #pragma unroll
       for (int d = 0; d < D; ++d) s += e[d] * w[d];
-      fo[b * Fp + f] = s;
+      sc.fo[b * Fp + f] = s;
     }
   }
   if (flags & kHasSecond) {
     // Y = U' E (rows k: fields, MT tiles of 16; columns n = b D + d of a sub-tile's 16 samples: D tiles of 16;
     // contraction over l: S steps of 4, from step 4 m on), second[b] = sum_{k, d} E[b, k, d] Y[k, b D + d]
-    constexpr int SMAX = 4 * kQMT;
+    constexpr int SMAX = 4 * kFMT;
     const int MT = p.MT, S = p.S;
-    float uf[kQMT][SMAX];
+    float uf[kFMT][SMAX];
     {
       const float* up = p.upack;
 #pragma unroll
-      for (int m = 0; m < kQMT; ++m)
+      for (int m = 0; m < kFMT; ++m)
 #pragma unroll
         for (int s = 0; s < SMAX; ++s) uf[m][s] = (m < MT && s >= 4 * m && s < S) ? up[(m * S + s) * 64 + lane] : 0.f;
     }
-    for (int it = wave; it < RT * D; it += kQW) {
+    for (int it = wave; it < RT * D; it += kFW) {
       const int rt = it / D;
       const int nt = it - rt * D;
       const int n = nt * 16 + (lane & 15);
       const int b = n / D;
       const int d = n - b * D;
       const float* ecol = etile + (rt * 16 + b) * SE + d;  // E[b][l][d] = ecol[l * D]
-      f32x4 acc[kQMT];
+      f32x4 acc[kFMT];
 #pragma unroll
-      for (int m = 0; m < kQMT; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int m = 0; m < kFMT; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int s0 = 0; s0 < SMAX; s0 += 4) {
         float bv[4];
@@ -353,13 +199,13 @@ int8_fused_kernel(const FwdArgs p, const Int8Geo q) {
 #pragma unroll
         for (int u = 0; u < 4; ++u)
 #pragma unroll
-          for (int m = 0; m < kQMT; ++m)
+          for (int m = 0; m < kFMT; ++m)
             if (4 * m <= s0 + u && s0 + u < S && m < MT)
               acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(uf[m][s0 + u], bv[u], acc[m], 0, 0, 0);
       }
       float colv = 0.f;
 #pragma unroll
-      for (int m = 0; m < kQMT; ++m) {
+      for (int m = 0; m < kFMT; ++m) {
         if (m < MT) {  // wave-uniform: the gather launch's kernel has exactly MT row tiles
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
@@ -370,33 +216,11 @@ int8_fused_kernel(const FwdArgs p, const Int8Geo q) {
       }
       colv += __shfl_xor(colv, 16);
       colv += __shfl_xor(colv, 32);
-      if (lane < 16) part2[rt * 16 * D + n] = colv;  // column n's sum over k (row tiles in order)
+      if (lane < 16) sc.part2[rt * 16 * D + n] = colv;  // column n's sum over k (row tiles in order)
     }
   }
   __syncthreads();
-  // first[b] (lw projection or plain sum over fields) and second[b] (sum over d): 16 lanes per sample each take
-  // every 16th term, then a 16-lane DPP sum
-  for (int g4 = wave; g4 * 4 < ROWS; g4 += kQW) {
-    const int b = g4 * 4 + (lane >> 4);
-    const int qd = lane & 15;
-    float first = 0.f, second = 0.f;
-    for (int f0 = 0; f0 < F; f0 += 64) {
-      float x[4], l[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int f = min(f0 + 16 * k + qd, F - 1);
-        x[k] = fo[b * Fp + f];
-        l[k] = (flags & kFoLw) ? lw_s[f] : 1.f;
-      }
-#pragma unroll
-      for (int k = 0; k < 4; ++k) first = f0 + 16 * k + qd < F ? fmaf(x[k], l[k], first) : first;
-    }
-    if (flags & kHasSecond)
-      for (int d = qd; d < D; d += 16) second += part2[b * D + d];  // the sample's column sums
-    first = sum16(first);
-    second = sum16(second);
-    if (qd == 0) fs[b] = first + second;
-  }
+  stage_fs<RT>(p, sc, fs, lane, wave);
 
   // ---- stage 2: the f32 E rows to int8.  Row b = tid / TPR, its float4s c4 = sub + TPR i in registers ----------------
   {
@@ -432,18 +256,18 @@ int8_fused_kernel(const FwdArgs p, const Int8Geo q) {
   for (int h = 0; h < p.H; ++h) {
     const bool last = h == p.H - 1;
     const int KC = h == 0 ? q.KC0 : q.KCN;
-    const u32x4* wt[kQTPW];
+    const u32x4* wt[kFTPW];
 #pragma unroll
-    for (int j = 0; j < kQTPW; ++j) {
-      int t = wave + kQW * j;
+    for (int j = 0; j < kFTPW; ++j) {
+      int t = wave + kFW * j;
       t = t < NT ? t : NT - 1;  // clamped duplicates, results discarded
       wt[j] = wl + (size_t)t * KC * 64;
     }
-    i32x4 acc[RT][kQTPW];
+    i32x4 acc[RT][kFTPW];
 #pragma unroll
     for (int i = 0; i < RT; ++i)
 #pragma unroll
-      for (int j = 0; j < kQTPW; ++j) acc[i][j] = i32x4{0, 0, 0, 0};
+      for (int j = 0; j < kFTPW; ++j) acc[i][j] = i32x4{0, 0, 0, 0};
     int8_k_loop<RT>(acc, wt, lane, qtile + rl * SQ + 16 * kq, 16 * SQ, KC);
     // the lane-derived epilogue values are recomputed per layer: hoisted out of the layer loop they stay live across
     // the K loops
@@ -454,13 +278,13 @@ int8_fused_kernel(const FwdArgs p, const Int8Geo q) {
 #pragma unroll
     for (int i = 0; i < RT; ++i) sxr[i] = sx_s[i * 16 + erl];
     // h = relu(fmaf((float)acc, sx[row] sw[n], b[n])) in place of the accumulators (the same registers, as floats)
-    f32x4 v[RT][kQTPW];
+    f32x4 v[RT][kFTPW];
     float mx[RT];
 #pragma unroll
     for (int i = 0; i < RT; ++i) mx[i] = 0.f;
 #pragma unroll
-    for (int j = 0; j < kQTPW; ++j) {
-      const int t = wave + kQW * j;
+    for (int j = 0; j < kFTPW; ++j) {
+      const int t = wave + kFW * j;
       const bool on = t < NT;  // wave-uniform
       const int n0 = (on ? t : 0) * 16 + 4 * ekq;
       const f32x4 sq = *reinterpret_cast<const f32x4*>(q.sw + (size_t)h * NT * 16 + n0);
@@ -481,14 +305,14 @@ int8_fused_kernel(const FwdArgs p, const Int8Geo q) {
       for (int i = 0; i < RT; ++i) {
         mx[i] = nanmax(mx[i], __shfl_xor(mx[i], 16));
         mx[i] = nanmax(mx[i], __shfl_xor(mx[i], 32));
-        if (lv < 16) wmax[(i * 16 + lv) * kQW + wave] = mx[i];
+        if (lv < 16) wmax[(i * 16 + lv) * kFW + wave] = mx[i];
       }
       __syncthreads();  // the maxes are there, and every wave has read the layer's input: the tile may be overwritten
 #pragma unroll
       for (int i = 0; i < RT; ++i) {
         const int row = i * 16 + erl;
-        const f32x4 m0 = *reinterpret_cast<const f32x4*>(wmax + row * kQW);
-        const f32x4 m1 = *reinterpret_cast<const f32x4*>(wmax + row * kQW + 4);
+        const f32x4 m0 = *reinterpret_cast<const f32x4*>(wmax + row * kFW);
+        const f32x4 m1 = *reinterpret_cast<const f32x4*>(wmax + row * kFW + 4);
         float a = 0.f;
 #pragma unroll
         for (int r = 0; r < 4; ++r) a = nanmax(a, m0[r]);
@@ -497,8 +321,8 @@ int8_fused_kernel(const FwdArgs p, const Int8Geo q) {
         const float inv = a == 0.f ? 0.f : 127.f / a;
         if (wave == 0 && lv < 16) sx_s[row] = a == 0.f ? 0.f : a / 127.f;
 #pragma unroll
-        for (int j = 0; j < kQTPW; ++j) {
-          const int t = wave + kQW * j;
+        for (int j = 0; j < kFTPW; ++j) {
+          const int t = wave + kFW * j;
           if (t < NT)  // wave-uniform
             *reinterpret_cast<uint32_t*>(qtile + row * SQ + t * 16 + 4 * ekq) =
                 quant4(v[i][j][0], v[i][j][1], v[i][j][2], v[i][j][3], inv);
@@ -506,21 +330,13 @@ int8_fused_kernel(const FwdArgs p, const Int8Geo q) {
       }
     } else {
 #pragma unroll
-      for (int j = 0; j < kQTPW; ++j) {
-        const int t = wave + kQW * j;
+      for (int j = 0; j < kFTPW; ++j) {
+        const int t = wave + kFW * j;
         if (t >= NT) break;  // wave-uniform
         const f32x4 fq = *reinterpret_cast<const f32x4*>(p.fc + t * 16 + 4 * ekq);
 #pragma unroll
-        for (int i = 0; i < RT; ++i) {  // uniform: every lane takes part in the shuffles
-          float d = 0.f;
-          d = fmaf(v[i][j][0], fq[0], d);
-          d = fmaf(v[i][j][1], fq[1], d);
-          d = fmaf(v[i][j][2], fq[2], d);
-          d = fmaf(v[i][j][3], fq[3], d);
-          d += __shfl_xor(d, 16);
-          d += __shfl_xor(d, 32);
-          if (lv < 16) part[(i * 16 + lv) * NT + t] = d;
-        }
+        for (int i = 0; i < RT; ++i)  // uniform: every lane takes part in the shuffles
+          last_layer_share(v[i][j], fq, lv, part + (i * 16 + lv) * NT + t);
       }
     }
     wl += (size_t)NT * KC * 64;
@@ -528,12 +344,7 @@ int8_fused_kernel(const FwdArgs p, const Int8Geo q) {
   }
 
   // ---- logit[b] = (first_second[b] + the shares in tile order) + bias ---------------------------------------------------
-  if (tid < ROWS && b0 + tid < p.batch) {
-    const float* pp = part + tid * NT;
-    float deep = pp[0];
-    for (int t = 1; t < NT; ++t) deep += pp[t];
-    tr.out[b0 + tid] = (fs[tid] + deep) + p.bias[0];
-  }
+  stage_logits<ROWS>(p, tr, part, fs, NT, tid);
 }
 
 // dfwfm_model_pack_int8: a workgroup per (layer, output tile of 16 neurons).  Sixteen lanes per neuron take the row's
@@ -599,10 +410,7 @@ __global__ void __launch_bounds__(256) int8_pack_kernel(const Int8PackArgs a) {
 template <int RT>
 hipError_t launch_rt(const FwdArgs& a, const Int8Geo& g, size_t lds, hipStream_t s) {
   auto k = (a.flags & kHasQR) ? int8_fused_kernel<RT, true> : int8_fused_kernel<RT, false>;
-  const hipError_t e = ensure_lds_limit(reinterpret_cast<const void*>(k), lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k, dim3(fwd_grid(a, 16 * RT)), dim3(kQTH), lds, s, a, g);
-  return hipGetLastError();
+  return launch_fused_kernel(k, a, g, 16 * RT, kFTH, lds, s);
 }
 
 inline int kc64(int cols) { return (cols + 63) / 64; }
@@ -623,7 +431,7 @@ Int8Geo int8_geo(int F, int D, int NT, int W0) {
 }  // namespace
 
 bool int8_supported(int F, int D, int H, int NT) {
-  return D == 10 && F >= 1 && F <= kQMaxF && H >= 1 && H <= kMaxH && NT >= 1 && NT <= kQW * kQTPW;
+  return D == 10 && F >= 1 && F <= kFMaxF && H >= 1 && H <= kMaxH && NT >= 1 && NT <= kFW * kFTPW;
 }
 
 size_t int8_pack_bytes(int F, int D, int H, int NT) {
@@ -663,7 +471,7 @@ hipError_t launch_int8_fused(const FwdArgs& a, const int8_t* w, const float* sw,
   g.sw = sw;
   g.b = b;
   const size_t lds = sizeof(float) * (size_t)int8_layout(rows, a.F, 10, a.NT, g.SE, g.SQ).total;
-  if (lds > kQLdsMax) return hipErrorInvalidValue;
+  if (lds > kFLdsMax) return hipErrorInvalidValue;
   switch (rows) {
     case 16: return launch_rt<1>(a, g, lds, s);
     case 32: return launch_rt<2>(a, g, lds, s);
