@@ -175,6 +175,27 @@ void free_model(dfwfm_model* m) {
   delete m;
 }
 
+// Who turns what stale.  A pack derived from the parameters registers in the set of every input it was built from; one
+// built on another pack goes with that pack (the bf16 fold: dfwfm_model_pack_bf16 drops it with the copy).
+
+// dfwfm_model_set_dense: new dense parameters
+void dense_changed(dfwfm_model* m) {
+  m->sp = 0;               // the sparse tower's ELL (the hidden layers' weights), until dfwfm_model_build_sparse_mlp
+  m->bf16_on = false;      // the bf16 copy of them, until dfwfm_model_pack_bf16
+  m->int8_on = false;      // the int8 pack of them, until dfwfm_model_pack_int8
+  m->fold_on = false;      // the folded layer 1 (W1), until dfwfm_model_fold_numerical
+  m->bf16fold_on = false;  // ... of the bf16 tower, until dfwfm_model_fold_bf16
+  m->flags &= ~kPairs;     // the FwFM pair list (R's nonzeros), until dfwfm_model_build_fwfm_pairs
+}
+
+// dfwfm_model_set_tables: new tables
+void tables_changed(dfwfm_model* m) {
+  m->pkw = 0;              // the serving copy (f32 or fp16) holds the old tables' rows
+  m->pkh = 0;
+  m->fold_on = false;      // the folded layer 1 holds row 0 of the old numerical tables
+  m->bf16fold_on = false;  // ... and so does the bf16 tower's
+}
+
 }  // namespace
 
 // FwFM second-order pieces (row tile m, column tile nt; S - 4m MFMA steps each) balanced over `nw` waves:
@@ -420,10 +441,7 @@ int dfwfm_model_set_tables(dfwfm_model* m, const dfwfm_field_tables* t, int32_t 
   for (int f = 0; f < n; ++f)
     if (host[f].c > 0) host[f].n = (host[f].n + host[f].c - 1) / host[f].c * host[f].c;
   memcpy(m->h_fields, host, sizeof(FieldDev) * n);
-  m->pkw = 0;  // the serving copy was built from the old tables
-  m->pkh = 0;
-  m->fold_on = false;  // and so was the folded layer 1 (the numerical tables' row 0)
-  m->bf16fold_on = false;
+  tables_changed(m);
   m->flags &= ~kHasQR;
   for (int f = 0; f < n; ++f)
     if (host[f].c > 0) m->flags |= kHasQR;
@@ -499,12 +517,7 @@ static int set_dense_impl(dfwfm_model* m, const float* field_cov, const float* f
   hipError_t e = launch_pack_list(L, blocks, s);
   if (e != hipSuccess) return hip_fail(e, "pack launch");
   m->dense_set = true;
-  m->sp = 0;  // new weights: the sparse tower's ELL is stale until rebuilt
-  m->bf16_on = false;  // and the bf16 copy until dfwfm_model_pack_bf16
-  m->fold_on = false;  // and the folded layer 1 until dfwfm_model_fold_numerical
-  m->bf16fold_on = false;  // ... of the bf16 tower until dfwfm_model_fold_bf16
-  m->int8_on = false;  // and the int8 pack until dfwfm_model_pack_int8
-  m->flags &= ~kPairs;  // and so is the FwFM pair list
+  dense_changed(m);
   for (int h = 0; h < m->H; ++h) m->lin_w[h] = lin_w ? lin_w[h] : nullptr;
   return DFWFM_OK;
 }
@@ -715,12 +728,19 @@ int diag_stamps_buffer(dfwfm_model* m, int64_t batch, int which, uint64_t** out)
 // until replaced, which only changes which (bit-identical) forward kernel runs.
 std::mutex g_cu_mu;
 
-int stream_cu_count(dfwfm_model* m, void* stream) {
+// the device's CUs (queried at the model's first call, so later calls are capturable into a graph)
+int device_cus(dfwfm_model* m) {
   std::lock_guard<std::mutex> lock(g_cu_mu);
   if (m->dev_cus == 0) {
     hipDeviceProp_t prop;
     m->dev_cus = hipGetDeviceProperties(&prop, m->device) == hipSuccess ? prop.multiProcessorCount : 256;
   }
+  return m->dev_cus;
+}
+
+int stream_cu_count(dfwfm_model* m, void* stream) {
+  const int dev = device_cus(m);  // ahead of this function's own lock: the mutex is not recursive
+  std::lock_guard<std::mutex> lock(g_cu_mu);
   const int cached = m->cu_n < 8 ? m->cu_n : 8;
   for (int i = 0; i < cached; ++i)
     if (m->cu_stream[i] == stream) return m->cu_count[i];
@@ -730,8 +750,7 @@ int stream_cu_count(dfwfm_model* m, void* stream) {
     for (int i = 0; i < 64; ++i) n += __builtin_popcount(mask[i]);
   } else {
     (void)hipGetLastError();
-    hipDeviceProp_t prop;
-    n = hipGetDeviceProperties(&prop, m->device) == hipSuccess ? prop.multiProcessorCount : 256;
+    n = dev;
   }
   const int slot = m->cu_n < 8 ? m->cu_n++ : (m->cu_next++ & 7);
   m->cu_stream[slot] = stream;
@@ -747,8 +766,46 @@ bool use_fwd32(dfwfm_model* m, int64_t batch, void* stream) {
   if (m->r32 == 0) return false;
   if (m->r32 == 2) return true;
   const int cus = stream_cu_count(m, stream);
-  const bool masked = cus < m->dev_cus;
+  const bool masked = cus < device_cus(m);
   return (batch + 31) / 32 >= (masked ? 1 : 2) * (int64_t)cus;
+}
+
+// a launch over a set of n batches (`tiles` workgroups each): their pointers; a lone batch keeps the plain arguments
+void fill_set(FwdArgs& a, int32_t n, int64_t tiles, const int64_t* const* xi, const float* const* xv,
+              float* const* out) {
+  if (n <= 1) return;
+  a.nb = n;
+  a.tiles = (int32_t)tiles;
+  for (int32_t j = 0; j < n; ++j) {
+    a.set_xi[j] = xi[j];
+    a.set_xv[j] = xv[j];
+    a.set_out[j] = out[j];
+  }
+}
+
+// The gather / shallow half of a deep model's forward as a launch of its own: the MLP-free forward's kernel (fwd_kernel
+// PART 3: the serving copy, the U'E FwFM pieces) storing the E tile [batch][NC0*16] and first + second [batch] instead
+// of the logit.  `what` names the launch in a HIP error.
+int launch_gather_half(const dfwfm_model* m, const int64_t* xi, int64_t xi_stride, const float* xv, int64_t xv_stride,
+                       int64_t batch, float* deep_emb, float* fs, void* stream, const char* what) {
+  FwdArgs a;
+  fill_forward_args(m, a, xi, xi_stride, xv, xv_stride, batch, nullptr);
+  a.flags &= ~kHasDeep;
+  if (m->MT <= 3) a.flags |= kP3Pieces;
+  a.part_stride = m->NC0 * 16;
+  a.part_e = deep_emb;
+  a.part_fs = fs;
+  hipError_t e = launch_forward(a, m->D, 1, 1, 8, m->lds_inf, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, what);
+  return DFWFM_OK;
+}
+
+// a caller's workspace against the `need` bytes that `sizer` (the *_workspace_bytes call) reports
+int check_workspace(const void* workspace, size_t ws_bytes, size_t need, const char* sizer) {
+  if (ws_bytes < need)
+    return fail(DFWFM_ERR_INVALID_ARG, "workspace of %zu bytes < %zu (%s)", ws_bytes, need, sizer);
+  if (reinterpret_cast<uintptr_t>(workspace) % 16) return fail(DFWFM_ERR_INVALID_ARG, "workspace not 16-byte aligned");
+  return DFWFM_OK;
 }
 
 }  // namespace
@@ -812,15 +869,7 @@ int dfwfm_forward_batches(dfwfm_model* m, int32_t nb, const int64_t* const* xi, 
     a.flags |= kPrio | kPrioEpi | kDeferTail;
     a.tail = m->tailI;
     apply_fold(m, a);
-    if (n > 1) {
-      a.nb = n;
-      a.tiles = (int32_t)((batch + rows - 1) / rows);
-      for (int32_t j = 0; j < n; ++j) {
-        a.set_xi[j] = xi[i0 + j];
-        a.set_xv[j] = xv[i0 + j];
-        a.set_out[j] = out[i0 + j];
-      }
-    }
+    fill_set(a, n, (batch + rows - 1) / rows, xi + i0, xv + i0, out + i0);
     int rc = diag_stamps_buffer(m, (int64_t)n * a.tiles * rows, 1, &a.stamps);
     if (rc != DFWFM_OK) return rc;
     const hipError_t e = r32 ? launch_fwd32(a, m->D, m->fold_on ? m->fold_lds_r32 : m->lds_r32, (hipStream_t)stream)
@@ -843,10 +892,8 @@ int dfwfm_forward_ws(dfwfm_model* m, const int64_t* xi, int64_t xi_stride, const
   if (!m->sp || !workspace) return dfwfm_forward(m, xi, xi_stride, xv, xv_stride, batch, out, stream);
   int rc = check_inputs(m, xi, xi_stride, xv, xv_stride, batch, out);
   if (rc != DFWFM_OK || batch == 0) return rc;
-  if (ws_bytes < split_ws_bytes(m, batch))
-    return fail(DFWFM_ERR_INVALID_ARG, "workspace of %zu bytes < %zu (dfwfm_forward_workspace_bytes)", ws_bytes,
-                split_ws_bytes(m, batch));
-  if (reinterpret_cast<uintptr_t>(workspace) % 16) return fail(DFWFM_ERR_INVALID_ARG, "workspace not 16-byte aligned");
+  rc = check_workspace(workspace, ws_bytes, split_ws_bytes(m, batch), "dfwfm_forward_workspace_bytes");
+  if (rc != DFWFM_OK) return rc;
   if (m->pkh)  // its gather launch reads the plain tables: it would serve the unrounded rows
     return fail(DFWFM_ERR_UNSUPPORTED, "the sparse deep tower does not read the fp16 serving copy");
   FwdArgs a;
@@ -895,22 +942,11 @@ int dfwfm_forward_gather(dfwfm_model* m, const int64_t* xi, int64_t xi_stride, c
   if (!deep_emb || deep_emb_stride != (int64_t)m->NC0 * 16)
     return fail(DFWFM_ERR_INVALID_ARG, "deep_emb stride %lld, need %d", (long long)deep_emb_stride, m->NC0 * 16);
   if (reinterpret_cast<uintptr_t>(deep_emb) % 16) return fail(DFWFM_ERR_INVALID_ARG, "deep_emb not 16-byte aligned");
-  // the MLP-free forward's kernel (fwd_kernel PART 3: the serving copy, the U'E FwFM pieces) storing the E tile and
-  // first + second instead of the logit
-  FwdArgs a;
-  fill_forward_args(m, a, xi, xi_stride, xv, xv_stride, batch, nullptr);
-  a.flags &= ~kHasDeep;
-  if (m->MT <= 3) a.flags |= kP3Pieces;
-  a.part_stride = m->NC0 * 16;
-  a.part_e = deep_emb;
-  a.part_fs = first_second;
-  hipError_t e = launch_forward(a, m->D, 1, 1, 8, m->lds_inf, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "gather launch");
-  return DFWFM_OK;
+  return launch_gather_half(m, xi, xi_stride, xv, xv_stride, batch, deep_emb, first_second, stream, "gather launch");
 }
 
-// The small-batch serving forward (include/dfwfm_serve.h): the gather / shallow half as dfwfm_forward_gather launches
-// it, into the caller's workspace, then the deep tower one launch per layer (dfwfm_serve.hip).
+// The small-batch serving forward (include/dfwfm_serve.h): the gather / shallow half (launch_gather_half) into the
+// caller's workspace, then the deep tower one launch per layer (dfwfm_serve.hip).
 int dfwfm_serve_abi_version(void) { return DFWFM_SERVE_ABI_VERSION; }
 
 int dfwfm_serve_workspace_bytes(dfwfm_model* m, int64_t batch, size_t* bytes) {
@@ -929,10 +965,9 @@ int dfwfm_serve_forward(dfwfm_model* m, const int64_t* xi, int64_t xi_stride, co
   int rc = check_inputs(m, xi, xi_stride, xv, xv_stride, batch, out);
   if (rc != DFWFM_OK || batch == 0) return rc;
   if (!workspace) return fail(DFWFM_ERR_INVALID_ARG, "null workspace");
-  const size_t need = sizeof(float) * serve_workspace_floats(m->NT, m->NC0, batch);
-  if (ws_bytes < need)
-    return fail(DFWFM_ERR_INVALID_ARG, "workspace of %zu bytes < %zu (dfwfm_serve_workspace_bytes)", ws_bytes, need);
-  if (reinterpret_cast<uintptr_t>(workspace) % 16) return fail(DFWFM_ERR_INVALID_ARG, "workspace not 16-byte aligned");
+  rc = check_workspace(workspace, ws_bytes, sizeof(float) * serve_workspace_floats(m->NT, m->NC0, batch),
+                       "dfwfm_serve_workspace_bytes");
+  if (rc != DFWFM_OK) return rc;
   const int64_t tiles = (batch + kBM - 1) / kBM;
   if (tiles * m->NT > 0x7fffffff) return fail(DFWFM_ERR_UNSUPPORTED, "batch too large for the serve forward");
   const size_t rows16 = (size_t)tiles * kBM;
@@ -948,16 +983,8 @@ int dfwfm_serve_forward(dfwfm_model* m, const int64_t* xi, int64_t xi_stride, co
   sa.act[1] = w;
   w += rows16 * m->NT * 16;
   sa.partial = w;
-  // the gather launch: the MLP-free forward's kernel storing the E tile and first + second (dfwfm_forward_gather)
-  FwdArgs a;
-  fill_forward_args(m, a, xi, xi_stride, xv, xv_stride, batch, nullptr);
-  a.flags &= ~kHasDeep;
-  if (m->MT <= 3) a.flags |= kP3Pieces;
-  a.part_stride = m->NC0 * 16;
-  a.part_e = deep_emb;
-  a.part_fs = fs;
-  hipError_t e = launch_forward(a, m->D, 1, 1, 8, m->lds_inf, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "serve gather launch");
+  rc = launch_gather_half(m, xi, xi_stride, xv, xv_stride, batch, deep_emb, fs, stream, "serve gather launch");
+  if (rc != DFWFM_OK) return rc;
   sa.deep_emb = deep_emb;
   sa.fs = fs;
   sa.wpack = m->d_wpack;
@@ -970,13 +997,13 @@ int dfwfm_serve_forward(dfwfm_model* m, const int64_t* xi, int64_t xi_stride, co
   sa.N = m->N;
   sa.NT = m->NT;
   sa.NC0 = m->NC0;
-  e = launch_serve_mlp(sa, (hipStream_t)stream);
+  hipError_t e = launch_serve_mlp(sa, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, "serve MLP launch");
   return DFWFM_OK;
 }
 
-// The bf16 deep tower (include/dfwfm_bf16.h): the gather / shallow half as dfwfm_forward_gather launches it, into the
-// caller's workspace, then the hidden layers on bf16 MFMA one launch per layer (dfwfm_bf16.hip).
+// The bf16 deep tower (include/dfwfm_bf16.h): the gather / shallow half (launch_gather_half) into the caller's
+// workspace, then the hidden layers on bf16 MFMA one launch per layer (dfwfm_bf16.hip).
 int dfwfm_bf16_abi_version(void) { return DFWFM_BF16_ABI_VERSION; }
 
 int dfwfm_model_pack_bf16(dfwfm_model* m, int enable, void* stream) {
@@ -1015,10 +1042,8 @@ int dfwfm_bf16_forward(dfwfm_model* m, const int64_t* xi, int64_t xi_stride, con
     return fail(DFWFM_ERR_STATE, "bf16 forward: the bf16 weight copy is absent or stale (dfwfm_model_pack_bf16)");
   if (batch == 0) return DFWFM_OK;
   if (!workspace) return fail(DFWFM_ERR_INVALID_ARG, "null workspace");
-  const size_t need = bf16_workspace_bytes(m->NT, m->NC0, batch);
-  if (ws_bytes < need)
-    return fail(DFWFM_ERR_INVALID_ARG, "workspace of %zu bytes < %zu (dfwfm_bf16_workspace_bytes)", ws_bytes, need);
-  if (reinterpret_cast<uintptr_t>(workspace) % 16) return fail(DFWFM_ERR_INVALID_ARG, "workspace not 16-byte aligned");
+  rc = check_workspace(workspace, ws_bytes, bf16_workspace_bytes(m->NT, m->NC0, batch), "dfwfm_bf16_workspace_bytes");
+  if (rc != DFWFM_OK) return rc;
   const int64_t tiles = (batch + kBM - 1) / kBM;
   if (tiles * m->NT > 0x7fffffff) return fail(DFWFM_ERR_UNSUPPORTED, "batch too large for the bf16 forward");
   const size_t rows16 = (size_t)tiles * kBM;
@@ -1033,16 +1058,8 @@ int dfwfm_bf16_forward(dfwfm_model* m, const int64_t* xi, int64_t xi_stride, con
   w += rows16 * m->NT;
   ba.act[0] = reinterpret_cast<uint16_t*>(w);
   ba.act[1] = ba.act[0] + rows16 * m->NT * 16;
-  // the gather launch: the MLP-free forward's kernel storing the E tile and first + second (dfwfm_forward_gather)
-  FwdArgs a;
-  fill_forward_args(m, a, xi, xi_stride, xv, xv_stride, batch, nullptr);
-  a.flags &= ~kHasDeep;
-  if (m->MT <= 3) a.flags |= kP3Pieces;
-  a.part_stride = m->NC0 * 16;
-  a.part_e = deep_emb;
-  a.part_fs = fs;
-  hipError_t e = launch_forward(a, m->D, 1, 1, 8, m->lds_inf, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "bf16 gather launch");
+  rc = launch_gather_half(m, xi, xi_stride, xv, xv_stride, batch, deep_emb, fs, stream, "bf16 gather launch");
+  if (rc != DFWFM_OK) return rc;
   ba.deep_emb = deep_emb;
   ba.fs = fs;
   ba.wb = m->d_wbf16;
@@ -1055,7 +1072,7 @@ int dfwfm_bf16_forward(dfwfm_model* m, const int64_t* xi, int64_t xi_stride, con
   ba.N = m->N;
   ba.NT = m->NT;
   ba.NC0 = m->NC0;
-  e = launch_bf16_mlp(ba, (hipStream_t)stream);
+  hipError_t e = launch_bf16_mlp(ba, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, "bf16 MLP launch");
   return DFWFM_OK;
 }
@@ -1083,35 +1100,150 @@ size_t fused_lds(const dfwfm_model* m, int rows, bool fold) {
 // (DESIGN.md section 3.12, 256 CUs): 16 rows win while they are at most one workgroup per CU (22.8 against 27.0 us at
 // 4096 rows), 32 rows from there on (30.4 against 34.1 at 8192, 184.9 against 286.0 at 81920); 64 rows (one workgroup
 // per CU by their LDS) never win (230.2 at 81920) and run only when forced: DFWFM_DIAG bf16rows=16 / 32 / 64 (tests,
-// A/B)
-int fused_rows(dfwfm_model* m, int64_t rows) {
-  const int forced = diag_opt("bf16rows", 0);
-  int64_t cus;
-  {  // the device's CUs (queried at the model's first call, so later calls are capturable into a graph)
-    std::lock_guard<std::mutex> lock(g_cu_mu);
-    if (m->dev_cus == 0) {
-      hipDeviceProp_t prop;
-      m->dev_cus = hipGetDeviceProperties(&prop, m->device) == hipSuccess ? prop.multiProcessorCount : 256;
-    }
-    cus = m->dev_cus;
-  }
-  auto fits = [&](int cand) { return fused_lds(m, cand, m->bf16fold_on) <= 160 * 1024; };
-  int r = 16;
-  if (forced == 32 || forced == 64) {
-    if (fits(forced)) r = forced;
-  } else if (forced == 0 && (rows + 15) / 16 > cus && fits(32)) {
-    r = 32;
-  }
-  return r;
+// A/B); the int8 forward follows the same rule and has no 64-row form: DFWFM_DIAG int8rows=16 / 32.
+// forced: the DFWFM_DIAG value, 0 when there is none; fits(r): whether r rows per workgroup are a form that fits in LDS
+template <typename Fits>
+int pick_rows(dfwfm_model* m, int64_t rows, int forced, Fits fits) {
+  const int64_t cus = device_cus(m);
+  if (forced == 32 || forced == 64) return fits(forced) ? forced : 16;
+  if (forced == 0 && (rows + 15) / 16 > cus && fits(32)) return 32;
+  return 16;
 }
 
-int fused_check(dfwfm_model* m) {
-  if (!m->cfg.use_deep) return fail(DFWFM_ERR_UNSUPPORTED, "bf16 fused forward: the model has no deep tower");
-  if (!fused_ok(m))
-    return fail(DFWFM_ERR_UNSUPPORTED,
-                "bf16 fused forward: shape not supported (embedding_size 10, field_size <= 48, deep_nodes <= 512, no "
-                "FwFM pair list); use dfwfm_bf16_forward");
+int fused_rows(dfwfm_model* m, int64_t rows) {
+  return pick_rows(m, rows, diag_opt("bf16rows", 0),
+                   [&](int r) { return fused_lds(m, r, m->bf16fold_on) <= 160 * 1024; });
+}
+
+// the int8 forward's shapes are the fused bf16 forward's, with the same condition on the gather's FwFM
+bool int8_ok(const dfwfm_model* m) {
+  return m->cfg.use_deep && int8_supported(m->F, m->D, m->H, m->NT) && m->MT <= 3 && !(m->flags & kPairs) &&
+         int8_lds_bytes(16, m->F, m->D, m->NT, m->W0) <= 160 * 1024;
+}
+
+int int8_rows(dfwfm_model* m, int64_t rows) {
+  return pick_rows(m, rows, diag_opt("int8rows", 0),
+                   [&](int r) { return r <= 32 && int8_lds_bytes(r, m->F, m->D, m->NT, m->W0) <= 160 * 1024; });
+}
+
+// What tells the one-launch forwards apart on the host: everything else is one_launch_forward_batches.
+struct OneLaunch {
+  const char* name;          // the messages' prefix
+  const char* unsupported;   // the message for a shape that `ok` refuses
+  const char* stale;         // ... and for a forward while the pack it reads is not `on`
+  bool (*ok)(const dfwfm_model*);
+  bool dfwfm_model::*on;
+  int (*rows)(dfwfm_model*, int64_t);
+  hipError_t (*launch)(const dfwfm_model*, const FwdArgs&, int rows, hipStream_t);
+};
+
+const OneLaunch kBf16Fused = {
+    "bf16 fused forward",
+    "bf16 fused forward: shape not supported (embedding_size 10, field_size <= 48, deep_nodes <= 512, no "
+    "FwFM pair list); use dfwfm_bf16_forward",
+    "bf16 fused forward: the bf16 weight copy is absent or stale (dfwfm_model_pack_bf16)",
+    fused_ok, &dfwfm_model::bf16_on, fused_rows,
+    [](const dfwfm_model* m, const FwdArgs& a, int rows, hipStream_t s) {
+      return launch_bf16_fused(a, m->d_wbf16, m->bf16fold_on ? m->d_wbf16f : nullptr, rows, s);
+    }};
+
+const OneLaunch kInt8 = {
+    "int8 forward",
+    "int8 forward: shape not supported (embedding_size 10, field_size <= 48, deep_nodes <= 512, no FwFM "
+    "pair list)",
+    "int8 forward: the int8 pack is absent or stale (dfwfm_model_pack_int8)",
+    int8_ok, &dfwfm_model::int8_on, int8_rows,
+    [](const dfwfm_model* m, const FwdArgs& a, int rows, hipStream_t s) {
+      return launch_int8_fused(a, m->d_wi8, m->d_i8s, m->d_i8s + (size_t)m->H * m->NT * 16, rows, s);
+    }};
+
+int one_launch_forward_batches(dfwfm_model* m, const OneLaunch& v, int32_t nb, const int64_t* const* xi,
+                               int64_t xi_stride, const float* const* xv, int64_t xv_stride, int64_t batch,
+                               float* const* out, void* stream) {
+  if (!m) return fail(DFWFM_ERR_INVALID_ARG, "null model");
+  if (nb < 0) return fail(DFWFM_ERR_INVALID_ARG, "negative batch count");
+  if (!m->cfg.use_deep) return fail(DFWFM_ERR_UNSUPPORTED, "%s: the model has no deep tower", v.name);
+  if (!v.ok(m)) return fail(DFWFM_ERR_UNSUPPORTED, "%s", v.unsupported);
+  if (nb == 0) return DFWFM_OK;
+  if (!xi || !xv || !out) return fail(DFWFM_ERR_INVALID_ARG, "null pointer array");
+  for (int32_t i = 0; i < nb; ++i) {
+    const int rc = check_inputs(m, xi[i], xi_stride, xv[i], xv_stride, batch, out[i]);
+    if (rc != DFWFM_OK) return rc;
+  }
+  if (!(m->*v.on)) return fail(DFWFM_ERR_STATE, "%s", v.stale);
+  if (batch == 0) return DFWFM_OK;
+  // the tile for the first launch's rows (a set of up to kMaxSet batches); later launches of a larger set use it too
+  const int64_t set = nb < kMaxSet ? nb : kMaxSet;
+  const int rows = v.rows(m, set * batch);
+  const int64_t tiles = (batch + rows - 1) / rows;
+  if (set * tiles > 0x7fffffff) return fail(DFWFM_ERR_UNSUPPORTED, "batch too large for the %s", v.name);
+  for (int32_t i0 = 0; i0 < nb; i0 += kMaxSet) {
+    FwdArgs a;
+    fill_forward_args(m, a, xi[i0], xi_stride, xv[i0], xv_stride, batch, out[i0]);
+    fill_set(a, nb - i0 < kMaxSet ? nb - i0 : kMaxSet, tiles, xi + i0, xv + i0, out + i0);
+    const hipError_t e = v.launch(m, a, rows, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, (std::string(v.name) + " launch").c_str());
+  }
   return DFWFM_OK;
+}
+
+// The serving copy of the categorical tables, f32 or fp16, up to its pack launch: whether the copy covers the model
+// (a second order, first-order tables, no QR field; *covered = false: nothing else done), its rows (*rows) of `pkw`
+// floats each in the grow-only d_pkrows, the pack launch's list L and the per-field row bases for d_pk.
+int plan_serving_copy(dfwfm_model* m, int pkw, PackTabList& L, const float** bases, size_t* rows, bool* covered) {
+  const int need = kHasSecond | kNeedE | kFoTables;
+  *covered = (m->flags & need) == need && !(m->flags & kHasQR) && m->F - m->num >= 1;
+  if (!*covered) return DFWFM_OK;
+  memset(&L, 0, sizeof L);
+  L.D = m->D;
+  L.pkw = pkw;
+  size_t total = 0;
+  for (int f = m->num; f < m->F; ++f) total += (size_t)m->h_fields[f].n;
+  *rows = total;
+  if (total * pkw > m->pkrows_floats) {
+    if (m->d_pkrows) (void)hipFree(m->d_pkrows);
+    m->d_pkrows = nullptr;
+    m->pkrows_floats = 0;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&m->d_pkrows), total * pkw * sizeof(float)));
+    m->pkrows_floats = total * pkw;
+  }
+  if (!m->d_pk) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&m->d_pk), 64 * sizeof(float*)));
+  size_t off = 0;
+  for (int f = m->num; f < m->F; ++f) {
+    const int j = f - m->num;
+    const int64_t n = m->h_fields[f].n;
+    bases[f] = m->d_pkrows + off;
+    L.emb2[j] = m->h_fields[f].emb2;
+    L.emb1[j] = m->h_fields[f].emb1;
+    L.dst[j] = m->d_pkrows + off;
+    L.n[j] = n;
+    const int64_t nb = (n + 255) / 256;
+    if ((int64_t)L.blk0[j] + nb > 0x7fffffff) return fail(DFWFM_ERR_UNSUPPORTED, "tables too large to pack");
+    L.blk0[j + 1] = L.blk0[j] + (int32_t)nb;
+    off += (size_t)n * pkw;
+  }
+  L.nf = m->F - m->num;
+  return DFWFM_OK;
+}
+
+// the tensor lists of dfwfm_adam_step / dfwfm_adam_step_dev: a tensor that is stepped (it has a grad) needs its state
+int adam_check(const dfwfm_adam_tensor* t, int32_t n) {
+  for (int i = 0; i < n; ++i)
+    if (t[i].grad && t[i].numel > 0 && (!t[i].param || !t[i].exp_avg || !t[i].exp_avg_sq))
+      return fail(DFWFM_ERR_INVALID_ARG, "adam tensor %d: null state pointer", i);
+  return DFWFM_OK;
+}
+
+// x as the next tensor of a launch's list, its `nb` workgroups behind the `blocks` of the tensors before it
+void adam_push(AdamList& list, int64_t& blocks, const dfwfm_adam_tensor& x, int64_t nb) {
+  AdamTensor& a = list.t[list.n];
+  a.p = x.param;
+  a.g = x.grad;
+  a.m = x.exp_avg;
+  a.v = x.exp_avg_sq;
+  a.n = x.numel;
+  list.block0[list.n++] = (int32_t)blocks;
+  blocks += nb;
 }
 
 }  // namespace
@@ -1127,91 +1259,16 @@ int dfwfm_bf16_fused_supported(dfwfm_model* m, int* supported) {
 int dfwfm_bf16_fused_forward_batches(dfwfm_model* m, int32_t nb, const int64_t* const* xi, int64_t xi_stride,
                                      const float* const* xv, int64_t xv_stride, int64_t batch, float* const* out,
                                      void* stream) {
-  if (!m) return fail(DFWFM_ERR_INVALID_ARG, "null model");
-  if (nb < 0) return fail(DFWFM_ERR_INVALID_ARG, "negative batch count");
-  int rc = fused_check(m);
-  if (rc != DFWFM_OK) return rc;
-  if (nb == 0) return DFWFM_OK;
-  if (!xi || !xv || !out) return fail(DFWFM_ERR_INVALID_ARG, "null pointer array");
-  for (int32_t i = 0; i < nb; ++i)
-    if ((rc = check_inputs(m, xi[i], xi_stride, xv[i], xv_stride, batch, out[i])) != DFWFM_OK) return rc;
-  if (!m->bf16_on)
-    return fail(DFWFM_ERR_STATE, "bf16 fused forward: the bf16 weight copy is absent or stale (dfwfm_model_pack_bf16)");
-  if (batch == 0) return DFWFM_OK;
-  // the tile for the first launch's rows (a set of up to kMaxSet batches); later launches of a larger set use it too
-  const int rows = fused_rows(m, (int64_t)(nb < kMaxSet ? nb : kMaxSet) * batch);
-  const int64_t tiles = (batch + rows - 1) / rows;
-  if ((int64_t)(nb < kMaxSet ? nb : kMaxSet) * tiles > 0x7fffffff)
-    return fail(DFWFM_ERR_UNSUPPORTED, "batch too large for the bf16 fused forward");
-  for (int32_t i0 = 0; i0 < nb; i0 += kMaxSet) {
-    const int32_t n = nb - i0 < kMaxSet ? nb - i0 : kMaxSet;
-    FwdArgs a;
-    fill_forward_args(m, a, xi[i0], xi_stride, xv[i0], xv_stride, batch, out[i0]);
-    if (n > 1) {
-      a.nb = n;
-      a.tiles = (int32_t)tiles;
-      for (int32_t j = 0; j < n; ++j) {
-        a.set_xi[j] = xi[i0 + j];
-        a.set_xv[j] = xv[i0 + j];
-        a.set_out[j] = out[i0 + j];
-      }
-    }
-    const hipError_t e = launch_bf16_fused(a, m->d_wbf16, m->bf16fold_on ? m->d_wbf16f : nullptr, rows,
-                                           (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "bf16 fused forward launch");
-  }
-  return DFWFM_OK;
+  return one_launch_forward_batches(m, kBf16Fused, nb, xi, xi_stride, xv, xv_stride, batch, out, stream);
 }
 
 int dfwfm_bf16_fused_forward(dfwfm_model* m, const int64_t* xi, int64_t xi_stride, const float* xv,
                              int64_t xv_stride, int64_t batch, float* out, void* stream) {
-  return dfwfm_bf16_fused_forward_batches(m, 1, &xi, xi_stride, &xv, xv_stride, batch, &out, stream);
+  return one_launch_forward_batches(m, kBf16Fused, 1, &xi, xi_stride, &xv, xv_stride, batch, &out, stream);
 }
 
 // The int8 deep tower in one launch (include/dfwfm_int8.h, dfwfm_int8.hip)
 int dfwfm_int8_abi_version(void) { return DFWFM_INT8_ABI_VERSION; }
-
-}  // extern "C"
-
-namespace {
-
-// the model's shape (the fused bf16 forward's set), and the gather's FwFM in the pieces form (no pair list)
-bool int8_ok(const dfwfm_model* m) {
-  return m->cfg.use_deep && int8_supported(m->F, m->D, m->H, m->NT) && m->MT <= 3 && !(m->flags & kPairs) &&
-         int8_lds_bytes(16, m->F, m->D, m->NT, m->W0) <= 160 * 1024;
-}
-
-// Rows per workgroup for a launch of `rows` rows: fused_rows' rule (16 rows while they are at most one workgroup per
-// CU, 32 from there on); DFWFM_DIAG int8rows=16 / 32 forces one (tests, A/B).  The logits do not depend on it.
-int int8_rows(dfwfm_model* m, int64_t rows) {
-  const int forced = diag_opt("int8rows", 0);
-  int64_t cus;
-  {  // the device's CUs (queried at the model's first call, so later calls are capturable into a graph)
-    std::lock_guard<std::mutex> lock(g_cu_mu);
-    if (m->dev_cus == 0) {
-      hipDeviceProp_t prop;
-      m->dev_cus = hipGetDeviceProperties(&prop, m->device) == hipSuccess ? prop.multiProcessorCount : 256;
-    }
-    cus = m->dev_cus;
-  }
-  const bool fits32 = int8_lds_bytes(32, m->F, m->D, m->NT, m->W0) <= 160 * 1024;
-  if (forced == 32) return fits32 ? 32 : 16;
-  if (forced == 0 && (rows + 15) / 16 > cus && fits32) return 32;
-  return 16;
-}
-
-int int8_check(dfwfm_model* m) {
-  if (!m->cfg.use_deep) return fail(DFWFM_ERR_UNSUPPORTED, "int8 forward: the model has no deep tower");
-  if (!int8_ok(m))
-    return fail(DFWFM_ERR_UNSUPPORTED,
-                "int8 forward: shape not supported (embedding_size 10, field_size <= 48, deep_nodes <= 512, no FwFM "
-                "pair list)");
-  return DFWFM_OK;
-}
-
-}  // namespace
-
-extern "C" {
 
 int dfwfm_model_pack_int8(dfwfm_model* m, void* stream) {
   if (!m) return fail(DFWFM_ERR_INVALID_ARG, "null model");
@@ -1248,45 +1305,12 @@ int dfwfm_int8_supported(dfwfm_model* m, int* supported) {
 int dfwfm_int8_forward_batches(dfwfm_model* m, int32_t nb, const int64_t* const* xi, int64_t xi_stride,
                                const float* const* xv, int64_t xv_stride, int64_t batch, float* const* out,
                                void* stream) {
-  if (!m) return fail(DFWFM_ERR_INVALID_ARG, "null model");
-  if (nb < 0) return fail(DFWFM_ERR_INVALID_ARG, "negative batch count");
-  int rc = int8_check(m);
-  if (rc != DFWFM_OK) return rc;
-  if (nb == 0) return DFWFM_OK;
-  if (!xi || !xv || !out) return fail(DFWFM_ERR_INVALID_ARG, "null pointer array");
-  for (int32_t i = 0; i < nb; ++i)
-    if ((rc = check_inputs(m, xi[i], xi_stride, xv[i], xv_stride, batch, out[i])) != DFWFM_OK) return rc;
-  if (!m->int8_on)
-    return fail(DFWFM_ERR_STATE, "int8 forward: the int8 pack is absent or stale (dfwfm_model_pack_int8)");
-  if (batch == 0) return DFWFM_OK;
-  // the tile for the first launch's rows (a set of up to kMaxSet batches); later launches of a larger set use it too
-  const int rows = int8_rows(m, (int64_t)(nb < kMaxSet ? nb : kMaxSet) * batch);
-  const int64_t tiles = (batch + rows - 1) / rows;
-  if ((int64_t)(nb < kMaxSet ? nb : kMaxSet) * tiles > 0x7fffffff)
-    return fail(DFWFM_ERR_UNSUPPORTED, "batch too large for the int8 forward");
-  for (int32_t i0 = 0; i0 < nb; i0 += kMaxSet) {
-    const int32_t n = nb - i0 < kMaxSet ? nb - i0 : kMaxSet;
-    FwdArgs a;
-    fill_forward_args(m, a, xi[i0], xi_stride, xv[i0], xv_stride, batch, out[i0]);
-    if (n > 1) {
-      a.nb = n;
-      a.tiles = (int32_t)tiles;
-      for (int32_t j = 0; j < n; ++j) {
-        a.set_xi[j] = xi[i0 + j];
-        a.set_xv[j] = xv[i0 + j];
-        a.set_out[j] = out[i0 + j];
-      }
-    }
-    const hipError_t e = launch_int8_fused(a, m->d_wi8, m->d_i8s, m->d_i8s + (size_t)m->H * m->NT * 16, rows,
-                                           (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "int8 forward launch");
-  }
-  return DFWFM_OK;
+  return one_launch_forward_batches(m, kInt8, nb, xi, xi_stride, xv, xv_stride, batch, out, stream);
 }
 
 int dfwfm_int8_forward(dfwfm_model* m, const int64_t* xi, int64_t xi_stride, const float* xv, int64_t xv_stride,
                        int64_t batch, float* out, void* stream) {
-  return dfwfm_int8_forward_batches(m, 1, &xi, xi_stride, &xv, xv_stride, batch, &out, stream);
+  return one_launch_forward_batches(m, kInt8, 1, &xi, xi_stride, &xv, xv_stride, batch, &out, stream);
 }
 
 // The folded layer 1 of the one-launch bf16 forward (include/dfwfm_bf16_fold.h)
@@ -1366,40 +1390,13 @@ int dfwfm_model_pack_tables(dfwfm_model* m, int32_t enable, int32_t* enabled, vo
   m->pkh = 0;
   if (!enable) return DFWFM_OK;
   if (!m->tables_set) return fail(DFWFM_ERR_STATE, "set_tables must precede pack_tables");
-  const int need = kHasSecond | kNeedE | kFoTables;
-  if ((m->flags & need) != need || (m->flags & kHasQR) || m->F - m->num < 1) return DFWFM_OK;
-  const int D = m->D;
-  const int pkw = D + 1 <= 16 ? 16 : (D + 4) & ~3;
+  const int pkw = m->D + 1 <= 16 ? 16 : (m->D + 4) & ~3;
   PackTabList L;
-  memset(&L, 0, sizeof L);
-  L.D = D;
-  L.pkw = pkw;
-  size_t rows = 0;
-  for (int f = m->num; f < m->F; ++f) rows += (size_t)m->h_fields[f].n;
-  if (rows * pkw > m->pkrows_floats) {
-    if (m->d_pkrows) (void)hipFree(m->d_pkrows);
-    m->d_pkrows = nullptr;
-    m->pkrows_floats = 0;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&m->d_pkrows), rows * pkw * sizeof(float)));
-    m->pkrows_floats = rows * pkw;
-  }
-  if (!m->d_pk) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&m->d_pk), 64 * sizeof(float*)));
   const float* bases[64] = {};
-  size_t off = 0;
-  for (int f = m->num; f < m->F; ++f) {
-    const int j = f - m->num;
-    const int64_t n = m->h_fields[f].n;
-    bases[f] = m->d_pkrows + off;
-    L.emb2[j] = m->h_fields[f].emb2;
-    L.emb1[j] = m->h_fields[f].emb1;
-    L.dst[j] = m->d_pkrows + off;
-    L.n[j] = n;
-    const int64_t nb = (n + 255) / 256;
-    if ((int64_t)L.blk0[j] + nb > 0x7fffffff) return fail(DFWFM_ERR_UNSUPPORTED, "tables too large to pack");
-    L.blk0[j + 1] = L.blk0[j] + (int32_t)nb;
-    off += (size_t)n * pkw;
-  }
-  L.nf = m->F - m->num;
+  size_t rows = 0;
+  bool covered = false;
+  const int rc = plan_serving_copy(m, pkw, L, bases, &rows, &covered);
+  if (rc != DFWFM_OK || !covered) return rc;
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipMemcpyAsync(m->d_pk, bases, sizeof bases, hipMemcpyHostToDevice, s));
   HIP_TRY(hipStreamSynchronize(s));  // `bases` is a stack buffer (once per weight update)
@@ -1424,40 +1421,14 @@ int dfwfm_model_pack_tables_half(dfwfm_model* m, int32_t enable, int32_t* enable
   m->pkh = 0;
   if (!enable) return DFWFM_OK;
   if (!m->tables_set) return fail(DFWFM_ERR_STATE, "set_tables must precede pack_tables_half");
-  const int need = kHasSecond | kNeedE | kFoTables;
-  if ((m->flags & need) != need || (m->flags & kHasQR) || m->F - m->num < 1) return DFWFM_OK;
   const int pkw = half_row_bytes(m->D) / 4;  // the row stride, in floats as the gathers index it
   PackTabList L;
-  memset(&L, 0, sizeof L);
-  L.D = m->D;
-  L.pkw = pkw;
-  size_t rows = 0;
-  for (int f = m->num; f < m->F; ++f) rows += (size_t)m->h_fields[f].n;
-  if (rows * pkw > m->pkrows_floats) {
-    if (m->d_pkrows) (void)hipFree(m->d_pkrows);
-    m->d_pkrows = nullptr;
-    m->pkrows_floats = 0;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&m->d_pkrows), rows * pkw * sizeof(float)));
-    m->pkrows_floats = rows * pkw;
-  }
-  if (!m->d_pk) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&m->d_pk), 64 * sizeof(float*)));
-  if (!m->d_pkovf) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&m->d_pkovf), sizeof(int32_t)));
   const float* bases[64] = {};
-  size_t off = 0;
-  for (int f = m->num; f < m->F; ++f) {
-    const int j = f - m->num;
-    const int64_t n = m->h_fields[f].n;
-    bases[f] = m->d_pkrows + off;
-    L.emb2[j] = m->h_fields[f].emb2;
-    L.emb1[j] = m->h_fields[f].emb1;
-    L.dst[j] = m->d_pkrows + off;
-    L.n[j] = n;
-    const int64_t nb = (n + 255) / 256;
-    if ((int64_t)L.blk0[j] + nb > 0x7fffffff) return fail(DFWFM_ERR_UNSUPPORTED, "tables too large to pack");
-    L.blk0[j + 1] = L.blk0[j] + (int32_t)nb;
-    off += (size_t)n * pkw;
-  }
-  L.nf = m->F - m->num;
+  size_t rows = 0;
+  bool covered = false;
+  const int rc = plan_serving_copy(m, pkw, L, bases, &rows, &covered);
+  if (rc != DFWFM_OK || !covered) return rc;
+  if (!m->d_pkovf) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&m->d_pkovf), sizeof(int32_t)));
   hipStream_t s = (hipStream_t)stream;
   // one wait for everything: `bases` is a stack buffer, and the overflow count comes back behind the pack launch
   int32_t over = 0;
@@ -2018,9 +1989,7 @@ int dfwfm_adam_step(const dfwfm_adam_tensor* t, int32_t n, double lr, double bet
   if (n > 0 && !t) return fail(DFWFM_ERR_INVALID_ARG, "null tensor list");
   if (n < 0) return fail(DFWFM_ERR_INVALID_ARG, "negative tensor count");
   if (step < 1) return fail(DFWFM_ERR_INVALID_ARG, "step must be >= 1");
-  for (int i = 0; i < n; ++i)
-    if (t[i].grad && t[i].numel > 0 && (!t[i].param || !t[i].exp_avg || !t[i].exp_avg_sq))
-      return fail(DFWFM_ERR_INVALID_ARG, "adam tensor %d: null state pointer", i);
+  if (int rc = adam_check(t, n)) return rc;
   // torch.optim.Adam: bias corrections and step size in double (Python floats), rounded to f32 per use
   const double bc1 = 1.0 - pow(beta1, (double)step);
   const double bc2 = 1.0 - pow(beta2, (double)step);
@@ -2044,14 +2013,7 @@ int dfwfm_adam_step(const dfwfm_adam_tensor* t, int32_t n, double lr, double bet
       int rc = flush();
       if (rc != DFWFM_OK) return rc;
     }
-    AdamTensor& a = list.t[list.n];
-    a.p = t[i].param;
-    a.g = t[i].grad;
-    a.m = t[i].exp_avg;
-    a.v = t[i].exp_avg_sq;
-    a.n = t[i].numel;
-    list.block0[list.n++] = (int32_t)blocks;
-    blocks += nb;
+    adam_push(list, blocks, t[i], nb);
   }
   return flush();
 }
@@ -2178,9 +2140,7 @@ int dfwfm_adam_step_dev(const dfwfm_adam_tensor* t, int32_t n, double lr, double
   if ((n > 0 && !t) || !state_dev) return fail(DFWFM_ERR_INVALID_ARG, "null argument");
   if (n < 0) return fail(DFWFM_ERR_INVALID_ARG, "negative tensor count");
   static_assert(sizeof(AdamDevState) == DFWFM_ADAM_STATE_BYTES, "state block size");
-  for (int i = 0; i < n; ++i)
-    if (t[i].grad && t[i].numel > 0 && (!t[i].param || !t[i].exp_avg || !t[i].exp_avg_sq))
-      return fail(DFWFM_ERR_INVALID_ARG, "adam tensor %d: null state pointer", i);
+  if (int rc = adam_check(t, n)) return rc;
   AdamDevState* st = reinterpret_cast<AdamDevState*>(state_dev);
   const AdamHyper h{lr, beta1, beta2, eps, weight_decay};
   // the tensors' launches (<= kAdamList tensors each); the last one advances the device step counter (a list
@@ -2202,15 +2162,7 @@ int dfwfm_adam_step_dev(const dfwfm_adam_tensor* t, int32_t n, double lr, double
       blocks = 0;
     }
     if (last) break;
-    const dfwfm_adam_tensor& x = t[keep[k]];
-    AdamTensor& a = list.t[list.n];
-    a.p = x.param;
-    a.g = x.grad;
-    a.m = x.exp_avg;
-    a.v = x.exp_avg_sq;
-    a.n = x.numel;
-    list.block0[list.n++] = (int32_t)blocks;
-    blocks += nb;
+    adam_push(list, blocks, t[keep[k]], nb);
   }
   if (keep.empty()) {
     hipError_t e = launch_adam_dev(list, 1, st, h, true, (hipStream_t)stream);

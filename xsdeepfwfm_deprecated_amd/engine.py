@@ -152,15 +152,19 @@ class ForwardEngine:
         """dfwfm_model_fold_numerical (include/dfwfm_fold.h): (re)build the folded layer 1 of the fused inference
         forward after a weight update (stream-ordered, no host synchronisation), or turn it off.  tables: the
         numerical fields' second-order tables (row 0 is folded into layer 1).  Returns whether the fold is on."""
+        return self._sync_fold("dfwfm_model_fold_numerical", "_fold_key", "_fold_on", tables, enable)
+
+    def _sync_fold(self, cname, key_attr, on_attr, tables, enable) -> bool:
+        """sync_fold / sync_bf16_fold: the C call when the dense parameters, a numerical table or `enable` changed
+        since the last one (the key and the answer are kept under key_attr / on_attr)."""
         key = (self._dense_key, tuple((t.data_ptr(), t._version) for t in tables), bool(enable))
-        if key == getattr(self, "_fold_key", None):
-            return self._fold_on
-        en = ctypes.c_int32(0)
-        _lib.check(_lib.lib().dfwfm_model_fold_numerical(self.handle, int(bool(enable)), ctypes.byref(en),
-                                                         _stream_handle(self.device)), "dfwfm_model_fold_numerical")
-        self._fold_on = bool(en.value)
-        self._fold_key = key
-        return self._fold_on
+        if key != getattr(self, key_attr, None):
+            en = ctypes.c_int32(0)
+            _lib.check(getattr(_lib.lib(), cname)(self.handle, int(bool(enable)), ctypes.byref(en),
+                                                  _stream_handle(self.device)), cname)
+            setattr(self, on_attr, bool(en.value))
+            setattr(self, key_attr, key)
+        return getattr(self, on_attr)
 
     def sync_packed(self, tables, enable: bool = True) -> bool:
         """dfwfm_model_pack_tables: the serving copy of the categorical tables (second-order row + first-order
@@ -275,119 +279,14 @@ class ForwardEngine:
         forward_bf16_batches after a weight update or a sync_bf16 (stream-ordered, no host synchronisation), or turn
         it off.  tables: the numerical fields' second-order tables (row 0 is folded into layer 1).  Call it after
         sync_bf16(True).  Returns whether the fold is on (False for a model that never folds)."""
-        key = (self._dense_key, tuple((t.data_ptr(), t._version) for t in tables), bool(enable))
-        if key == getattr(self, "_bf16_fold_key", None):
-            return self._bf16_fold_on
-        en = ctypes.c_int32(0)
-        _lib.check(_lib.lib().dfwfm_model_fold_bf16(self.handle, int(bool(enable)), ctypes.byref(en),
-                                                    _stream_handle(self.device)), "dfwfm_model_fold_bf16")
-        self._bf16_fold_on = bool(en.value)
-        self._bf16_fold_key = key
-        return self._bf16_fold_on
+        return self._sync_fold("dfwfm_model_fold_bf16", "_bf16_fold_key", "_bf16_fold_on", tables, enable)
 
     # -- hot path ----------------------------------------------------------
-    def forward(self, xi: torch.Tensor, xv: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
-        B = xi.shape[0]
-        if self.int8 and B > 0:
-            return self.forward_int8(xi, xv, out)
-        if self.bf16 and B > 0:
-            return self.forward_bf16_fused(xi, xv, out) if self.bf16_fused else self.forward_bf16(xi, xv, out)
-        if 0 < B <= self.small_rows:
-            return self.forward_small(xi, xv, out)
-        ncat = self.cfg["field_size"] - self.cfg["numerical"]
-        num = self.cfg["numerical"]
-        _require_rows(xi, "Xi", torch.int64, self.device, ncat)
-        _require_rows(xv, "Xv", torch.float32, self.device, num)
-        if out is None:
-            out = torch.empty(B, dtype=torch.float32, device=self.device)
-        xs = xi.stride(0) if ncat > 0 else 0
-        vs = xv.stride(0) if num > 0 else 0
-        ws_bytes = self._ws_bytes(B)
-        # split forward (gather launch + MLP launch): its workspace comes from torch's stream-ordered
-        # caching allocator, so batches in flight on several streams never share one
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device) if ws_bytes else None
-        rc = _lib.lib().dfwfm_forward_ws(self.handle, ctypes.c_void_p(xi.data_ptr()), xs,
-                                         ctypes.c_void_p(xv.data_ptr()), vs, B,
-                                         ctypes.c_void_p(out.data_ptr()), _ptr(ws), ws_bytes,
-                                         _stream_handle(self.device))
-        _lib.check(rc, "dfwfm_forward")
-        return out
-
-    def forward_small(self, xi: torch.Tensor, xv: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
-        """dfwfm_serve_forward (include/dfwfm_serve.h): the low-latency forward of a small batch -- the gather launch,
-        then every hidden layer as its own launch with a workgroup per 16 x 16 output tile, so a handful of rows use
-        many CUs instead of one.  Deep models only (DfwfmError otherwise).  Logits agree with forward() to rounding
-        (another fixed summation order); a row's bits do not depend on the batch around it."""
-        B = xi.shape[0]
-        ncat = self.cfg["field_size"] - self.cfg["numerical"]
-        num = self.cfg["numerical"]
-        _require_rows(xi, "Xi", torch.int64, self.device, ncat)
-        _require_rows(xv, "Xv", torch.float32, self.device, num)
-        if out is None:
-            out = torch.empty(B, dtype=torch.float32, device=self.device)
-        xs = xi.stride(0) if ncat > 0 else 0
-        vs = xv.stride(0) if num > 0 else 0
-        ws_bytes = self._serve_ws_bytes(B)
-        # from torch's stream-ordered caching allocator: calls in flight on several streams never share one
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device) if ws_bytes else None
-        rc = _lib.lib().dfwfm_serve_forward(self.handle, ctypes.c_void_p(xi.data_ptr()), xs,
-                                            ctypes.c_void_p(xv.data_ptr()), vs, B,
-                                            ctypes.c_void_p(out.data_ptr()), _ptr(ws), ws_bytes,
-                                            _stream_handle(self.device))
-        _lib.check(rc, "dfwfm_serve_forward")
-        return out
-
-    def _serve_ws_bytes(self, B: int) -> int:
-        cache = self.__dict__.setdefault("_serve_ws_cache", {})  # a function of the model's shape and B alone
-        if B not in cache:
-            n = ctypes.c_size_t(0)
-            _lib.check(_lib.lib().dfwfm_serve_workspace_bytes(self.handle, B, ctypes.byref(n)),
-                       "dfwfm_serve_workspace_bytes")
-            cache[B] = int(n.value)
-        return cache[B]
-
-    def forward_bf16(self, xi: torch.Tensor, xv: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
-        """dfwfm_bf16_forward (include/dfwfm_bf16.h): the forward with the hidden layers on bf16 MFMA (f32
-        accumulation; gather, first order and FwFM in exact f32), after sync_bf16(True).  Deep models only
-        (DfwfmError otherwise).  A row's bits do not depend on the batch around it."""
-        B = xi.shape[0]
-        ncat = self.cfg["field_size"] - self.cfg["numerical"]
-        num = self.cfg["numerical"]
-        _require_rows(xi, "Xi", torch.int64, self.device, ncat)
-        _require_rows(xv, "Xv", torch.float32, self.device, num)
-        if out is None:
-            out = torch.empty(B, dtype=torch.float32, device=self.device)
-        xs = xi.stride(0) if ncat > 0 else 0
-        vs = xv.stride(0) if num > 0 else 0
-        ws_bytes = self._bf16_ws_bytes(B)
-        # from torch's stream-ordered caching allocator: calls in flight on several streams never share one
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device) if ws_bytes else None
-        rc = _lib.lib().dfwfm_bf16_forward(self.handle, ctypes.c_void_p(xi.data_ptr()), xs,
-                                           ctypes.c_void_p(xv.data_ptr()), vs, B,
-                                           ctypes.c_void_p(out.data_ptr()), _ptr(ws), ws_bytes,
-                                           _stream_handle(self.device))
-        _lib.check(rc, "dfwfm_bf16_forward")
-        return out
-
-    def _bf16_ws_bytes(self, B: int) -> int:
-        cache = self.__dict__.setdefault("_bf16_ws_cache", {})  # a function of the model's shape and B alone
-        if B not in cache:
-            n = ctypes.c_size_t(0)
-            _lib.check(_lib.lib().dfwfm_bf16_workspace_bytes(self.handle, B, ctypes.byref(n)),
-                       "dfwfm_bf16_workspace_bytes")
-            cache[B] = int(n.value)
-        return cache[B]
-
-    def bf16_fused_supported(self) -> bool:
-        """dfwfm_bf16_fused_supported: whether forward_bf16_fused / forward_bf16_batches run this model (its shape,
-        and no FwFM pair list on); host-only."""
-        v = ctypes.c_int(0)
-        _lib.check(_lib.lib().dfwfm_bf16_fused_supported(self.handle, ctypes.byref(v)), "dfwfm_bf16_fused_supported")
-        return bool(v.value)
-
-    def forward_bf16_fused(self, xi: torch.Tensor, xv: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
-        """dfwfm_bf16_fused_forward (include/dfwfm_bf16_fused.h): forward_bf16 in one launch and without a workspace,
-        after sync_bf16(True); the same bits.  DfwfmError for a shape bf16_fused_supported() refuses."""
+    def _call_forward(self, method, cname, xi, xv, out, ws_bytes=None, check_as=None):
+        """One lone-batch forward of the C ABI for the public `method`: the checks of the inputs and of `out` (made
+        here when None), the strides, and the call.  ws_bytes: for a call that takes a workspace, B -> its bytes; the
+        workspace comes from torch's stream-ordered caching allocator, so calls in flight on several streams never
+        share one.  check_as: the name an error reports, when it is not cname."""
         B = xi.shape[0]
         ncat = self.cfg["field_size"] - self.cfg["numerical"]
         num = self.cfg["numerical"]
@@ -396,17 +295,80 @@ class ForwardEngine:
         if out is None:
             out = torch.empty(B, dtype=torch.float32, device=self.device)
         elif out.numel() < B:
-            raise ValueError("forward_bf16_fused: output smaller than the batch")
+            raise ValueError(f"{method}: output smaller than the batch")
         xs = xi.stride(0) if ncat > 0 else 0
         vs = xv.stride(0) if num > 0 else 0
-        rc = _lib.lib().dfwfm_bf16_fused_forward(self.handle, ctypes.c_void_p(xi.data_ptr()), xs,
-                                                 ctypes.c_void_p(xv.data_ptr()), vs, B,
-                                                 ctypes.c_void_p(out.data_ptr()), _stream_handle(self.device))
-        _lib.check(rc, "dfwfm_bf16_fused_forward")
+        fn = getattr(_lib.lib(), cname)
+        if ws_bytes is None:
+            rc = fn(self.handle, ctypes.c_void_p(xi.data_ptr()), xs, ctypes.c_void_p(xv.data_ptr()), vs, B,
+                    ctypes.c_void_p(out.data_ptr()), _stream_handle(self.device))
+        else:
+            n = ws_bytes(B)
+            ws = torch.empty(n, dtype=torch.uint8, device=self.device) if n else None
+            rc = fn(self.handle, ctypes.c_void_p(xi.data_ptr()), xs, ctypes.c_void_p(xv.data_ptr()), vs, B,
+                    ctypes.c_void_p(out.data_ptr()), _ptr(ws), n, _stream_handle(self.device))
+        _lib.check(rc, check_as or cname)
         return out
 
-    def _batch_set_args(self, batches, outs, what):
-        """The argument checks of a batch set: (nb, B, xs, vs, pxi, pxv, pout) for the C call."""
+    def _cached_ws_bytes(self, cache_attr, cname, B: int) -> int:
+        """The workspace bytes that `cname` reports for a batch of B rows, asked once per B (cache_attr: the dict's
+        name; "_ws_cache" is dropped when the sparse tower changes, the others depend on the model's shape alone)."""
+        cache = self.__dict__.setdefault(cache_attr, {})
+        if B not in cache:
+            n = ctypes.c_size_t(0)
+            _lib.check(getattr(_lib.lib(), cname)(self.handle, B, ctypes.byref(n)), cname)
+            cache[B] = int(n.value)
+        return cache[B]
+
+    def _supported(self, cname) -> bool:
+        v = ctypes.c_int(0)
+        _lib.check(getattr(_lib.lib(), cname)(self.handle, ctypes.byref(v)), cname)
+        return bool(v.value)
+
+    def forward(self, xi: torch.Tensor, xv: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+        B = xi.shape[0]
+        if self.int8 and B > 0:
+            return self.forward_int8(xi, xv, out)
+        if self.bf16 and B > 0:
+            return self.forward_bf16_fused(xi, xv, out) if self.bf16_fused else self.forward_bf16(xi, xv, out)
+        if 0 < B <= self.small_rows:
+            return self.forward_small(xi, xv, out)
+        # with a sparse deep tower the split forward (gather launch + MLP launch), which needs a workspace
+        return self._call_forward(
+            "forward", "dfwfm_forward_ws", xi, xv, out,
+            lambda b: self._cached_ws_bytes("_ws_cache", "dfwfm_forward_workspace_bytes", b), check_as="dfwfm_forward")
+
+    def forward_small(self, xi: torch.Tensor, xv: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+        """dfwfm_serve_forward (include/dfwfm_serve.h): the low-latency forward of a small batch -- the gather launch,
+        then every hidden layer as its own launch with a workgroup per 16 x 16 output tile, so a handful of rows use
+        many CUs instead of one.  Deep models only (DfwfmError otherwise).  Logits agree with forward() to rounding
+        (another fixed summation order); a row's bits do not depend on the batch around it."""
+        return self._call_forward(
+            "forward_small", "dfwfm_serve_forward", xi, xv, out,
+            lambda b: self._cached_ws_bytes("_serve_ws_cache", "dfwfm_serve_workspace_bytes", b))
+
+    def forward_bf16(self, xi: torch.Tensor, xv: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+        """dfwfm_bf16_forward (include/dfwfm_bf16.h): the forward with the hidden layers on bf16 MFMA (f32
+        accumulation; gather, first order and FwFM in exact f32), after sync_bf16(True).  Deep models only
+        (DfwfmError otherwise).  A row's bits do not depend on the batch around it."""
+        return self._call_forward(
+            "forward_bf16", "dfwfm_bf16_forward", xi, xv, out,
+            lambda b: self._cached_ws_bytes("_bf16_ws_cache", "dfwfm_bf16_workspace_bytes", b))
+
+    def bf16_fused_supported(self) -> bool:
+        """dfwfm_bf16_fused_supported: whether forward_bf16_fused / forward_bf16_batches run this model (its shape,
+        and no FwFM pair list on); host-only."""
+        return self._supported("dfwfm_bf16_fused_supported")
+
+    def forward_bf16_fused(self, xi: torch.Tensor, xv: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+        """dfwfm_bf16_fused_forward (include/dfwfm_bf16_fused.h): forward_bf16 in one launch and without a workspace,
+        after sync_bf16(True); the same bits.  DfwfmError for a shape bf16_fused_supported() refuses."""
+        return self._call_forward("forward_bf16_fused", "dfwfm_bf16_fused_forward", xi, xv, out)
+
+    def _call_forward_set(self, cname, batches, outs, what) -> list:
+        """One batch-set forward of the C ABI for the public method `what`: the checks of the set, then the call."""
+        if len(batches) == 0:
+            return outs
         nb = len(batches)
         if len(outs) != nb:
             raise ValueError(f"{what}: one output per batch")
@@ -428,68 +390,36 @@ class ForwardEngine:
         pxi = P(*[xi.data_ptr() for xi, _ in batches])
         pxv = P(*[xv.data_ptr() for _, xv in batches])
         pout = P(*[o.data_ptr() for o in outs])
-        return nb, B, xs, vs, pxi, pxv, pout
+        rc = getattr(_lib.lib(), cname)(self.handle, nb, pxi, xs, pxv, vs, B, pout, _stream_handle(self.device))
+        _lib.check(rc, cname)
+        return outs
 
     def forward_bf16_batches(self, batches, outs) -> list:
         """dfwfm_bf16_fused_forward_batches: forward_bf16_fused of every (xi, xv) in `batches` (same batch size and row
         strides), one launch per 32 batches; logits into outs[i], bit-identical to forward_bf16 on each batch alone."""
-        if len(batches) == 0:
-            return outs
-        nb, B, xs, vs, pxi, pxv, pout = self._batch_set_args(batches, outs, "forward_bf16_batches")
-        rc = _lib.lib().dfwfm_bf16_fused_forward_batches(self.handle, nb, pxi, xs, pxv, vs, B, pout,
-                                                         _stream_handle(self.device))
-        _lib.check(rc, "dfwfm_bf16_fused_forward_batches")
-        return outs
+        return self._call_forward_set("dfwfm_bf16_fused_forward_batches", batches, outs, "forward_bf16_batches")
 
     def int8_supported(self) -> bool:
         """dfwfm_int8_supported: whether forward_int8 / forward_int8_batches run this model (its shape, and no FwFM
         pair list on); host-only."""
-        v = ctypes.c_int(0)
-        _lib.check(_lib.lib().dfwfm_int8_supported(self.handle, ctypes.byref(v)), "dfwfm_int8_supported")
-        return bool(v.value)
+        return self._supported("dfwfm_int8_supported")
 
     def forward_int8(self, xi: torch.Tensor, xv: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
         """dfwfm_int8_forward (include/dfwfm_int8.h): the forward with the hidden layers on int8 MFMA (weights
         quantized per neuron, activations per row and layer; gather, first order and FwFM in exact f32) in one launch,
         after sync_int8(True).  DfwfmError for a shape int8_supported() refuses.  A row's bits do not depend on the
         batch around it."""
-        B = xi.shape[0]
-        ncat = self.cfg["field_size"] - self.cfg["numerical"]
-        num = self.cfg["numerical"]
-        _require_rows(xi, "Xi", torch.int64, self.device, ncat)
-        _require_rows(xv, "Xv", torch.float32, self.device, num)
-        if out is None:
-            out = torch.empty(B, dtype=torch.float32, device=self.device)
-        elif out.numel() < B:
-            raise ValueError("forward_int8: output smaller than the batch")
-        xs = xi.stride(0) if ncat > 0 else 0
-        vs = xv.stride(0) if num > 0 else 0
-        rc = _lib.lib().dfwfm_int8_forward(self.handle, ctypes.c_void_p(xi.data_ptr()), xs,
-                                           ctypes.c_void_p(xv.data_ptr()), vs, B,
-                                           ctypes.c_void_p(out.data_ptr()), _stream_handle(self.device))
-        _lib.check(rc, "dfwfm_int8_forward")
-        return out
+        return self._call_forward("forward_int8", "dfwfm_int8_forward", xi, xv, out)
 
     def forward_int8_batches(self, batches, outs) -> list:
         """dfwfm_int8_forward_batches: forward_int8 of every (xi, xv) in `batches` (same batch size and row strides),
         one launch per 32 batches; logits into outs[i], bit-identical to forward_int8 on each batch alone."""
-        if len(batches) == 0:
-            return outs
-        nb, B, xs, vs, pxi, pxv, pout = self._batch_set_args(batches, outs, "forward_int8_batches")
-        rc = _lib.lib().dfwfm_int8_forward_batches(self.handle, nb, pxi, xs, pxv, vs, B, pout,
-                                                   _stream_handle(self.device))
-        _lib.check(rc, "dfwfm_int8_forward_batches")
-        return outs
+        return self._call_forward_set("dfwfm_int8_forward_batches", batches, outs, "forward_int8_batches")
 
     def forward_batches(self, batches, outs) -> list:
         """dfwfm_forward_batches: the forward of every (xi, xv) in `batches` (same batch size and row strides),
         all in one launch per 32 batches; logits into outs[i], bit-identical to forward() on each batch alone."""
-        if len(batches) == 0:
-            return outs
-        nb, B, xs, vs, pxi, pxv, pout = self._batch_set_args(batches, outs, "forward_batches")
-        rc = _lib.lib().dfwfm_forward_batches(self.handle, nb, pxi, xs, pxv, vs, B, pout, _stream_handle(self.device))
-        _lib.check(rc, "dfwfm_forward_batches")
-        return outs
+        return self._call_forward_set("dfwfm_forward_batches", batches, outs, "forward_batches")
 
     def forward_gather(self, xi: torch.Tensor, xv: torch.Tensor, deep_emb: torch.Tensor | None = None,
                        first_second: torch.Tensor | None = None):
@@ -512,15 +442,6 @@ class ForwardEngine:
                                              _stream_handle(self.device))
         _lib.check(rc, "dfwfm_forward_gather")
         return deep_emb, first_second
-
-    def _ws_bytes(self, B: int) -> int:
-        cache = self.__dict__.setdefault("_ws_cache", {})
-        if B not in cache:
-            n = ctypes.c_size_t(0)
-            _lib.check(_lib.lib().dfwfm_forward_workspace_bytes(self.handle, B, ctypes.byref(n)),
-                       "dfwfm_forward_workspace_bytes")
-            cache[B] = int(n.value)
-        return cache[B]
 
     # -- training step -------------------------------------------------------
     def train_forward(self, xi, xv, out, dropout_p: float, seed: int) -> int:
