@@ -55,7 +55,7 @@ def test_train_variant_matches_float64(gpu, name, det):
     """Logits, loss, every gradient (per tensor; per touched table row; untouched rows exactly 0) and the Adam
     update.  f64: F = 64, num = 16, D = 10, N = 256 needs 37 972 floats = 148.3 KiB of backward LDS (bwd_layout:
     lw 64 + fwlw 640 + rsk 4096 + E 16 x 644 + dE 16 x 644 + G / Gram 8192 + dl 16 + fc 260 + tail 2048 + fo 1024 +
-    xv 1024), under the 160 KiB refusal; its 136 tensors take Adam's 40-tensor launches four times."""
+    xv 1024), under the 160 KiB refusal; its 136 tensors take Adam's 91-tensor launches (kAdamList) twice."""
     cfg, params, xi, xv, y = tc.case(name)
     ref, (_, _, og, onew) = tc.reference(name)
     m = build(cfg, params, gpu, is_deep_dropout=False)
