@@ -17,9 +17,9 @@
  *      FwFM / FM second order are the expressions of the one-launch bf16 forward's stage 1, so first + second are the
  *      bits dfwfm_forward_gather writes, and x_0 is the f32 deep_emb row (E in field order).
  *   1. Weights, formed once by dfwfm_model_pack_int8.  For layer l and neuron n:
- *        aw       = max_k |W_l[n, k]|
+ *        aw       = max_k |W_l[n, k]|; the max propagates NaN, as the activations' max of step 2 does
  *        sw[l][n] = aw / 127, or 1 when aw == 0
- *        qW[n, k] = clamp(rint(W_l[n, k] / sw[l][n]), -127, 127)
+ *        qW[n, k] = clamp(rint(W_l[n, k] / sw[l][n]), -127, 127); 0 where W_l[n, k] / sw[l][n] is NaN
  *      padded neurons and padded k are 0.
  *   2. Activations, per row and per layer:
  *        a    = max_k |x_{l-1}[k]| over the layer's real K inputs; the max propagates NaN
@@ -37,6 +37,10 @@
  *     size, the row's position, the row tile chosen or the batch set.
  *   - A row whose tower input holds a NaN or an infinity gets a NaN logit (a = inf: every q is 0, acc = 0 times
  *     sx = inf is NaN; a = NaN: sx is NaN).  Other rows are untouched.
+ *   - A neuron whose weight row holds a NaN or an infinity is NaN for every row (aw = NaN: sw is NaN; aw = inf: every
+ *     qW is 0 and acc = 0 times sw = inf is NaN), and so is every logit, as in the f32 and bf16 forwards of the same
+ *     model.  A NaN or infinite bias, fc weight or model bias reaches the logits through the f32 steps 4 and 6.  A
+ *     diverged model is never served as a finite one.
  *   - This is not fbgemm's dynamic quantization (one activation scale per tensor over the whole batch, 7-bit
  *     activations, per-tensor weights), which would make a row's logit depend on its batch neighbours.
  *

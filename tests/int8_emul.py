@@ -17,11 +17,15 @@ SWEEP_UNSUPPORTED = [i for i in range(len(SWEEP)) if i not in SWEEP_SUPPORTED]
 
 def quantize_weights(W):
     """(qW float64 array of integers in [-127, 127], sw float32 [N]) of a layer's f32 weights [N, K]: per neuron
-    aw = max |W|, sw = aw / 127 (1 for a zero row), qW = clamp(rint(W / sw)) -- f32 division, ties to even."""
+    aw = max |W| (NaN kept), sw = aw / 127 (1 for a zero row), qW = clamp(rint(W / sw)) -- f32 division, ties to even
+    --, 0 where W / sw is NaN.  A row that holds a NaN has sw = NaN, one that holds an infinity sw = inf; both have
+    qW = 0."""
     W = np.asarray(W, dtype=f32)
-    aw = np.abs(W).max(axis=1).astype(f32)
-    sw = np.where(aw == 0, f32(1), aw / f32(127)).astype(f32)
-    q = np.rint((W / sw[:, None]).astype(f32))
+    with np.errstate(all="ignore"):
+        aw = np.abs(W).max(axis=1).astype(f32)  # np.max propagates NaN
+        sw = np.where(aw == 0, f32(1), aw / f32(127)).astype(f32)
+        q = np.rint((W / sw[:, None]).astype(f32))
+        q = np.where(np.isnan(q), f32(0), q)
     return np.clip(q, -127, 127).astype(np.float64), sw
 
 
@@ -41,9 +45,9 @@ def quantize_rows(x):
 
 
 def tower(cfg, params, x, fma=True, return_hidden=False):
-    """h_H (float32 [B, N]) of the contract from the f32 tower input x [B, K].  fma: the epilogue as one fused
-    multiply-add (a float64 product -- exact for a 24-bit by 24-bit value -- plus add, rounded once to f32); False: a
-    f32 multiply, then a f32 add (the other rounding a kernel might use)."""
+    """h_H (float32 [B, N]) of the contract from the f32 tower input x [B, K]; rows and weights may hold NaN or inf.
+    fma: the epilogue as one fused multiply-add (a float64 product -- exact for a 24-bit by 24-bit value -- plus add,
+    rounded once to f32); False: a f32 multiply, then a f32 add (the other rounding a kernel might use)."""
     H = cfg["h_depth"]
     hidden = []
     h = None
@@ -52,7 +56,8 @@ def tower(cfg, params, x, fma=True, return_hidden=False):
         b = np.asarray(params[f"net_1_linear_{l}.bias"], dtype=f32)
         q, sx, _ = quantize_rows(x)
         acc = q @ qW.T  # integers below 2^24: exact in float64 in any order
-        assert np.abs(acc).max() < 2 ** 24
+        # q and qW are finite whatever x and W hold (a NaN quotient is 0): what is not finite enters through sx, sw, b
+        assert np.abs(acc).max(initial=0) < 2 ** 24  # (false for a NaN too)
         with np.errstate(all="ignore"):
             t = (sx[:, None] * sw[None, :]).astype(f32)
             if fma:

@@ -69,6 +69,16 @@ def test_weight_quantizer_edges():
     assert sw[1] == f32(1) / f32(127) and q[1].tolist() == [127, -64, 32, 0]  # 63.5 and 31.75 (ties to even, nearest)
     assert q[2].tolist()[:2] == [-127, 127] and np.abs(q).max() == 127
     assert sw[3] == 1 and q[3].tolist() == [127, 64, 64, -62]  # exact ties round to even
+    # a NaN or an infinity in a row: the max keeps it, sw is NaN or inf, every qW is 0 -- and the neuron is NaN for
+    # every input row, a zero row included (0 times sw is NaN either way)
+    W = np.array([[1, np.nan, -2, 0], [1, np.inf, -2, 0], [-np.inf, 5, 0, 0], [1, -0.5, 0.25, 0]], dtype=f32)
+    q, sw = int8_emul.quantize_weights(W)
+    assert np.isnan(sw[0]) and np.isposinf(sw[1]) and np.isposinf(sw[2]) and sw[3] == f32(1) / f32(127)
+    assert (q[:3] == 0).all() and q[3].tolist() == [127, -64, 32, 0] and np.isfinite(q).all()
+    cfg = dict(h_depth=1)
+    x = np.array([[1, 2, 3, 4], [0, 0, 0, 0]], dtype=f32)
+    h = int8_emul.tower(cfg, {"net_1_linear_1.weight": W, "net_1_linear_1.bias": np.ones(4, dtype=f32)}, x)
+    assert np.isnan(h[:, :3]).all() and np.isfinite(h[:, 3]).all() and h[1, 3] == 1
 
 
 def test_row_quantizer_edges():

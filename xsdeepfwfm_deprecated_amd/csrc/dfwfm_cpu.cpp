@@ -299,7 +299,7 @@ void forward_block(const Model& P, int64_t b0, int64_t nb, const int64_t* xi, in
       for (int64_t i = 0; i < nb; ++i) {
         float* y = Bf.data() + i * ld0;
         for (int n = 0; n < N; ++n) {
-          float v = y[n] > 0.f ? y[n] : 0.f;  // ReLU (NaN -> NaN is irrelevant here: finite inputs)
+          float v = y[n] < 0.f ? 0.f : y[n];  // ReLU that keeps a NaN, as the device's relu_keep_nan
           if (drop) v = keep(seed, l + 1, b0 + i, n, drop_p) ? v * scale : 0.f;
           y[n] = v;
         }

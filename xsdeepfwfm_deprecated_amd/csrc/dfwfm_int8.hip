@@ -348,9 +348,10 @@ int8_fused_kernel(const FwdArgs p, const Int8Geo q) {
 }
 
 // dfwfm_model_pack_int8: a workgroup per (layer, output tile of 16 neurons).  Sixteen lanes per neuron take the row's
-// max |W| (a 16-lane shuffle tree); sw = aw / 127, or 1 for a zero row; then a thread per (K step, lane) writes its 16
-// weights of neuron n = 16 t + (l & 15), k = 64 c + 16 (l >> 4) + 0..15, as clamp(rint(W / sw), -127, 127), zero
-// outside [N][K].  The tile's sw and biases (the padded f32 biases of set_dense) go beside the pack.
+// max |W| (a 16-lane shuffle tree that keeps a NaN: sw is then NaN and the neuron NaN for every row, never an ordinary
+// zero); sw = aw / 127, or 1 for a zero row; then a thread per (K step, lane) writes its 16 weights of neuron
+// n = 16 t + (l & 15), k = 64 c + 16 (l >> 4) + 0..15, as clamp(rint(W / sw), -127, 127), zero outside [N][K].  The
+// tile's sw and biases (the padded f32 biases of set_dense) go beside the pack.
 struct Int8PackArgs {
   const float* w[kMaxH];  // the caller's weights of the last set_dense, [N][K_l] row-major
   const float* mlp_b;     // [H][NT*16] padded biases (model-owned, written by set_dense on the stream)
@@ -372,9 +373,9 @@ __global__ void __launch_bounds__(256) int8_pack_kernel(const Int8PackArgs a) {
     const int n = t * 16 + (tid >> 4);
     float aw = 0.f;
     if (n < a.N)
-      for (int k = tid & 15; k < K; k += 16) aw = fmaxf(aw, fabsf(w[(size_t)n * K + k]));
+      for (int k = tid & 15; k < K; k += 16) aw = nanmax(aw, fabsf(w[(size_t)n * K + k]));
 #pragma unroll
-    for (int o = 1; o < 16; o *= 2) aw = fmaxf(aw, __shfl_xor(aw, o));
+    for (int o = 1; o < 16; o *= 2) aw = nanmax(aw, __shfl_xor(aw, o));
     if ((tid & 15) == 0) {
       const float s = aw == 0.f ? 1.f : aw / 127.f;
       sw_s[tid >> 4] = s;
