@@ -66,8 +66,8 @@ int dfwfm_half_tables_abi_version(void);
 int dfwfm_model_pack_tables_half(dfwfm_model* m, int32_t enable, int32_t* enabled, int64_t* overflow_count,
                                  void* stream);
 
-/* *bytes = the size of the serving copy in use (rows x row stride, f32 or fp16), or 0 when the model reads the plain
- * tables; host-only, no launch. */
+/* *bytes = the size of the serving copy in use (rows x row stride: f32, fp16, or the int8 one of
+ * dfwfm_int8_tables.h), or 0 when the model reads the plain tables; host-only, no launch. */
 int dfwfm_model_serving_copy_bytes(dfwfm_model* m, int64_t* bytes);
 
 #ifdef __cplusplus

@@ -25,6 +25,9 @@ def main(argv=None):
     if pars.table_dtype == "fp16" and not (pars.use_cuda and pars.time_on_cuda and torch.cuda.is_available()):
         # before any training: the fp16 serving copy is HIP only, and both models (fit's evaluation, the benchmark) use it
         parser.error("-table_dtype fp16 needs -use_cuda 1 -time_on_cuda 1 and a HIP device")
+    if pars.table_dtype == "int8" and not (pars.use_cuda and pars.time_on_cuda and torch.cuda.is_available()):
+        # as for fp16: the int8 serving copy is HIP only
+        parser.error("-table_dtype int8 needs -use_cuda 1 -time_on_cuda 1 and a HIP device")
     np.random.seed(pars.random_seed)
     random.seed(pars.random_seed)
     torch.manual_seed(pars.random_seed)

@@ -9,6 +9,7 @@ Prints one JSON line.
 
   python tools/latency.py [--calls 1000] [--batches 1,16,64,256,1024,4096,8192] [--small] [--bf16] [--bf16-fused] [--int8]
   python tools/latency.py --half-tables [--rounds 7]
+  python tools/latency.py --int8-tables [--rounds 7]
 
 --small: the small-batch serving forward (eng.forward_small, include/dfwfm_serve.h) measured beside eng.forward at
 every batch, same figures, under models["deepfwfm_small"] (the batch where it stops winning is the value to give
@@ -39,6 +40,9 @@ hipGraph so that launch overhead is not what is compared.  Rows, in us per 4096-
 and as a 20-batch set, the deep f32 forward, the fused bf16 forward and the int8 forward as 20-batch sets -- at the
 Criteo-39 table sizes and with every categorical table 8 times as long (HBM-resident).  Also the copies' bytes and
 the pack time.
+
+--int8-tables: the same measurement over three modules, one per copy: f32, fp16 and the int8 one
+(include/dfwfm_int8_tables.h), timed in turns f32, fp16, int8; the same rows, scales, copy bytes and pack times.
 """
 import argparse
 import json
@@ -132,13 +136,17 @@ def measure_batch_set(call, xi, xv, out, dev, reps=10):
     return e0.elapsed_time(e1) * 1e3 / reps, nb
 
 
-def half_tables(rounds, dev):
-    """--half-tables: see the module docstring."""
+def half_tables(rounds, dev, dtypes=("f32", "fp16")):
+    """--half-tables, and --int8-tables with dtypes = ("f32", "fp16", "int8"): see the module docstring."""
     from xsdeepfwfm_deprecated_amd import DeepFMs, synth
     B, NB = 4096, 20
-    res = {"what": "f32 serving copy of the categorical tables against the fp16 one (DeepFMs.table_dtype), us per "
-                   "4096-row batch, hipGraph replays, the two copies timed in turns; median [min, max] over rounds",
-           "rounds": rounds, "batch": B, "set": NB, "scales": {}}
+    if len(dtypes) == 2:
+        what = ("f32 serving copy of the categorical tables against the fp16 one (DeepFMs.table_dtype), us per "
+                "4096-row batch, hipGraph replays, the two copies timed in turns; median [min, max] over rounds")
+    else:
+        what = ("f32, fp16 and int8 serving copies of the categorical tables (DeepFMs.table_dtype), us per 4096-row "
+                "batch, hipGraph replays, the three copies timed in turns; median [min, max] over rounds")
+    res = {"what": what, "rounds": rounds, "batch": B, "set": NB, "scales": {}}
 
     def module(sizes, deep, dtype):
         m = DeepFMs(field_size=39, feature_sizes=sizes, embedding_size=10, use_fwfm=1, use_fm=0, use_deep=deep,
@@ -187,13 +195,13 @@ def half_tables(rounds, dev):
             for deep in (0, 1):
                 graphs = {}  # row -> {dtype: (graph, calls in it, batches per call)}
                 keep = []
-                for dtype in ("f32", "fp16"):
+                for dtype in dtypes:
                     m = module(sizes, deep, dtype)
                     keep.append(m)
                     eng = m._sync_inference(dev)
                     torch.cuda.synchronize(dev)
                     ts = []
-                    for _ in range(3):  # the pack alone: one launch and the wait dfwfm_model_pack_tables[_half] makes
+                    for _ in range(3):  # the pack alone: one launch and the wait the pack call makes
                         eng._packed_key = None
                         t0 = time.perf_counter()
                         m._sync_inference(dev)
@@ -216,13 +224,15 @@ def half_tables(rounds, dev):
                     for row, (fn, n, per) in calls.items():
                         graphs.setdefault(row, {})[dtype] = (graph_of(fn, n), n, per)
                 for row, by in graphs.items():
-                    t = {"f32": [], "fp16": []}
+                    t = {dtype: [] for dtype in dtypes}
                     for _ in range(rounds):
-                        for dtype in ("f32", "fp16"):
+                        for dtype in dtypes:
                             g, n, per = by[dtype]
                             t[dtype].append(timed(g, n, 20) / per)
-                    sc["us_per_batch"][row] = {"f32": summary(t["f32"]), "fp16": summary(t["fp16"]),
-                                               "fp16_over_f32": round(float(np.median(t["fp16"]) / np.median(t["f32"])), 4)}
+                    sc["us_per_batch"][row] = {dtype: summary(t[dtype]) for dtype in dtypes}
+                    for dtype in dtypes[1:]:
+                        sc["us_per_batch"][row][dtype + "_over_f32"] = round(
+                            float(np.median(t[dtype]) / np.median(t["f32"])), 4)
                 del graphs, keep
                 torch.cuda.empty_cache()
         res["scales"][str(scale)] = sc
@@ -241,12 +251,14 @@ def main():
                     help="also measure eng.forward_int8 and eng.forward_int8_batches (deep model)")
     ap.add_argument("--half-tables", action="store_true",
                     help="only this: the f32 serving copy of the tables against the fp16 one (see the docstring)")
-    ap.add_argument("--rounds", type=int, default=7, help="--half-tables: timed turns per copy and row")
+    ap.add_argument("--int8-tables", action="store_true",
+                    help="only this: the f32, fp16 and int8 serving copies of the tables (see the docstring)")
+    ap.add_argument("--rounds", type=int, default=7, help="--half-tables / --int8-tables: timed turns per copy and row")
     a = ap.parse_args()
-    if a.half_tables:
+    if a.half_tables or a.int8_tables:
         dev = torch.device("cuda", 0)
         torch.cuda.set_device(dev)
-        return half_tables(a.rounds, dev)
+        return half_tables(a.rounds, dev, ("f32", "fp16", "int8") if a.int8_tables else ("f32", "fp16"))
     a.bf16 = a.bf16 or a.bf16_fused
     batches = [int(x) for x in a.batches.split(",")]
     if not batches or min(batches) < 1 or max(batches) > 81920:

@@ -114,7 +114,12 @@ class DeepFMs(nn.Module):
         # whose categorical second-order tables are w.half().float().  Inference on a HIP device only; training reads
         # the f32 tables.  One path, no fallback: a model the copy does not cover (QR fields, fwlw without first-order
         # tables), pack_tables = False, a CPU module, small_batch_rows > 0, the per-layer bf16 forward, a sparse deep
-        # tower or a value that overflows fp16 raise DfwfmError rather than serve unrounded rows
+        # tower or a value that overflows fp16 raise DfwfmError rather than serve unrounded rows.
+        # "int8": each categorical second-order row quantized once to row-wise symmetric int8 under a bf16 scale, the
+        # first-order weight kept f32, a quarter of the f32 copy's bytes and one 16-byte load per row at embedding_size
+        # 10 (include/dfwfm_int8_tables.h).  The logits are those of the same path on a model
+        # whose categorical second-order tables are the dequantized values q * s.  The same contract as "fp16": one
+        # path, no fallback, DfwfmError in the same cases and for a value that is NaN, +-inf or >= 2^127 in magnitude
         self.table_dtype = "f32"
         # the fused inference forward folds the numerical fields into layer 1 of the deep tower (their embedding is
         # Xv * v_f[0], so layer 1 takes Xv * P with P = W1 v_f[0] precomputed after each weight update: 18 K chunks
@@ -306,13 +311,17 @@ class DeepFMs(nn.Module):
             for f in range(self.num, self.field_size):
                 d = self._field_desc(None if second is None else second[f], None if first is None else first[f])
                 tabs.append((d["emb2"], d["emb1"]))
-            if self._half_tables():
+            dt = self._table_dtype()
+            if dt != "f32":
                 if not self.pack_tables:
-                    raise DfwfmError("table_dtype='fp16' is the serving copy's storage: it needs pack_tables = True")
+                    raise DfwfmError(f"table_dtype='{dt}' is the serving copy's storage: it needs pack_tables = True")
                 if self.use_deep and int(getattr(self, "small_batch_rows", 0)) > 0:
-                    raise DfwfmError("table_dtype='fp16': the small-batch serving path (small_batch_rows > 0) is not "
-                                     "part of the fp16 tables' contract")
-                eng.sync_packed_half(tabs)
+                    raise DfwfmError(f"table_dtype='{dt}': the small-batch serving path (small_batch_rows > 0) is not "
+                                     f"part of the {dt} tables' contract")
+                if dt == "int8":
+                    eng.sync_packed_int8(tabs)
+                else:
+                    eng.sync_packed_half(tabs)
             else:
                 eng.sync_packed(tabs, self.pack_tables)
             if self.use_deep:  # the folded layer 1, rebuilt when W1 or a numerical table changed
@@ -328,25 +337,30 @@ class DeepFMs(nn.Module):
             self._half_tables_paths(eng)
         return eng
 
+    def _table_dtype(self) -> str:
+        """table_dtype, validated (here: at the next forward)."""
+        dt = getattr(self, "table_dtype", "f32")
+        if dt not in ("f32", "fp16", "int8"):
+            raise ValueError(f"table_dtype must be 'f32', 'fp16' or 'int8', got {dt!r}")
+        return dt
+
     def _half_tables(self) -> bool:
         """Whether table_dtype asks for the fp16 serving copy (validated here: at the next forward)."""
-        dt = getattr(self, "table_dtype", "f32")
-        if dt not in ("f32", "fp16"):
-            raise ValueError(f"table_dtype must be 'f32' or 'fp16', got {dt!r}")
-        return dt == "fp16"
+        return self._table_dtype() == "fp16"
 
     def _half_tables_paths(self, eng, settled=False):
-        """With table_dtype = 'fp16': refuse the forwards outside its contract; settled: the forward has synced the
-        pair list and the sparse tower (the sparse tower's state is current only then)."""
-        if not self._half_tables() or not self.use_deep:
+        """With table_dtype = 'fp16' or 'int8': refuse the forwards outside its contract; settled: the forward has
+        synced the pair list and the sparse tower (the sparse tower's state is current only then)."""
+        dt = self._table_dtype()
+        if dt == "f32" or not self.use_deep:
             return
         if eng.bf16 and not eng.bf16_fused:
-            raise DfwfmError("table_dtype='fp16' with mlp_dtype='bf16' needs the one-launch form (bf16_fused = True "
+            raise DfwfmError(f"table_dtype='{dt}' with mlp_dtype='bf16' needs the one-launch form (bf16_fused = True "
                              "on a shape it supports, no FwFM pair list): the per-layer bf16 forward is not part of "
-                             "the fp16 tables' contract")
+                             f"the {dt} tables' contract")
         if settled and not eng.int8 and not eng.bf16 and getattr(eng, "_sparse_on", False):
-            raise DfwfmError("table_dtype='fp16': the sparse deep tower (sparse_mlp_max_density > 0) reads the plain "
-                             "tables; it is not part of the fp16 tables' contract")
+            raise DfwfmError(f"table_dtype='{dt}': the sparse deep tower (sparse_mlp_max_density > 0) reads the plain "
+                             f"tables; it is not part of the {dt} tables' contract")
 
     def _mlp_bf16(self) -> bool:
         """Whether mlp_dtype asks for the bf16 deep tower (validated here: at the next forward)."""
@@ -438,7 +452,7 @@ class DeepFMs(nn.Module):
     # ---------------------------------------------------------------- forward
     def forward(self, Xi, Xv):
         device = self._device()
-        half = self._half_tables()  # (a bad table_dtype raises here, whatever the mode)
+        tdt = self._table_dtype()  # (a bad table_dtype raises here, whatever the mode)
         eng = self._sync_engine(device)
         xi, xv = self._prep_inputs(Xi, Xv, device)
         needs_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
@@ -452,8 +466,9 @@ class DeepFMs(nn.Module):
         if device.type == "cpu" and getattr(self, "mlp_dtype", "f32") == "int8":
             raise DfwfmError("mlp_dtype='int8' is the HIP-only int8 MFMA path (include/dfwfm_int8.h); "
                              "a CPU model runs mlp_dtype='f32'")
-        if device.type == "cpu" and half:
-            raise DfwfmError("table_dtype='fp16' is the HIP serving copy's storage (include/dfwfm_half_tables.h); "
+        if device.type == "cpu" and tdt != "f32":
+            hdr = "dfwfm_int8_tables.h" if tdt == "int8" else "dfwfm_half_tables.h"
+            raise DfwfmError(f"table_dtype='{tdt}' is the HIP serving copy's storage (include/{hdr}); "
                              "a CPU model runs table_dtype='f32'")
         if device.type != "cpu":  # (the host kernel has no serving copy or pruned-layout variants)
             self._sync_inference(device)  # the tables' serving copy, re-packed after weight updates

@@ -44,7 +44,8 @@ HEADERS = ["dfwfm_internal.h", "dfwfm_device.h", "dfwfm_fused_stage.h", "dfwfm_a
            os.path.join("..", "..", "include", "dfwfm_bf16_fused.h"), os.path.join("..", "..", "include", "dfwfm_fold.h"),
            os.path.join("..", "..", "include", "dfwfm_bf16_fold.h"), os.path.join("..", "..", "include", "dfwfm_int8.h"),
            os.path.join("..", "..", "include", "dfwfm_lazy_adam.h"),
-           os.path.join("..", "..", "include", "dfwfm_half_tables.h")]
+           os.path.join("..", "..", "include", "dfwfm_half_tables.h"),
+           os.path.join("..", "..", "include", "dfwfm_int8_tables.h")]
 ARCH = os.environ.get("DFWFM_OFFLOAD_ARCH", "gfx950")
 CPU_PATH = os.path.join(PKG_DIR, "libdfwfm_cpu.so")
 CPU_SOURCES = ["dfwfm_cpu.cpp"]
@@ -235,6 +236,14 @@ HALF_TABLES_SIGNATURES = {
     "dfwfm_model_pack_tables_half": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
                                                     ctypes.POINTER(ctypes.c_int64), _P]),
     "dfwfm_model_serving_copy_bytes": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int64)]),
+}
+
+# the int8 serving copy of the categorical tables (include/dfwfm_int8_tables.h): same library, its own header and ABI
+# version
+INT8_TABLES_SIGNATURES = {
+    "dfwfm_int8_tables_abi_version": (ctypes.c_int, []),
+    "dfwfm_model_pack_tables_int8": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
+                                                    ctypes.POINTER(ctypes.c_int64), _P]),
 }
 
 _lib = None
@@ -478,6 +487,12 @@ def lib():
             fn.argtypes = args
         if L.dfwfm_half_tables_abi_version() != 1:
             raise DfwfmError("libdfwfm half tables ABI mismatch")
+        for name, (res, args) in INT8_TABLES_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        if L.dfwfm_int8_tables_abi_version() != 1:
+            raise DfwfmError("libdfwfm int8 tables ABI mismatch")
         _lib = L
     return _lib
 

@@ -75,9 +75,10 @@ def get_parser():
     a("-bf16_fold", default=0, type=int, choices=[0, 1],
       help="with -mlp_dtype bf16 -bf16_fused 1: the numerical fields folded into layer 1 of the one-launch bf16 "
            "forward (DeepFMs.bf16_fold; another rounding of the same size; a model that cannot fold stays unfolded)")
-    a("-table_dtype", default="f32", type=str, choices=["f32", "fp16"],
+    a("-table_dtype", default="f32", type=str, choices=["f32", "fp16", "int8"],
       help="storage of the inference forward's serving copy of the categorical tables: f32, or fp16 second-order rows "
-           "rounded once per weight update, half the bytes (HIP only; this engine's addition, DeepFMs.table_dtype; "
+           "rounded once per weight update, half the bytes, or int8 second-order rows under one bf16 scale per row, a "
+           "quarter of the bytes (HIP only; this engine's addition, DeepFMs.table_dtype; "
            "QR tables, the small-batch, per-layer bf16 and sparse paths raise)")
     a("-lazy_adam", default=0, type=int, choices=[0, 1],
       help="training on a HIP device with Adam: the categorical tables' Adam updates only the rows each batch touched "
@@ -133,6 +134,6 @@ def get_model(cuda, feature_sizes, pars, dynamic_quantization=False, static_quan
     m.mlp_dtype = getattr(pars, "mlp_dtype", "f32")  # a CPU model with "bf16" raises at its first forward
     m.bf16_fused = bool(getattr(pars, "bf16_fused", 0))
     m.bf16_fold = bool(getattr(pars, "bf16_fold", 0))
-    m.table_dtype = getattr(pars, "table_dtype", "f32")  # a CPU model with "fp16" raises at its first forward
+    m.table_dtype = getattr(pars, "table_dtype", "f32")  # a CPU model with "fp16" or "int8" raises at its first forward
     m.lazy_table_adam = bool(getattr(pars, "lazy_adam", 0))  # fit() raises if the fused Adam step is not the path
     return m

@@ -20,6 +20,7 @@
 #include "../../include/dfwfm_fold.h"
 #include "../../include/dfwfm_lazy_adam.h"
 #include "../../include/dfwfm_half_tables.h"
+#include "../../include/dfwfm_int8_tables.h"
 
 using namespace dfwfm;
 
@@ -59,9 +60,10 @@ struct dfwfm_model {
   size_t pkrows_floats;  // capacity
   const float** d_pk;    // [64] per-field row bases (device)
   int pkw;               // row stride in floats while the copy is in use, else 0
-  int pkh;               // 1 while the copy in use is the fp16 one (dfwfm_model_pack_tables_half), else 0
+  int pkh;               // the format of the copy in use (FwdArgs::pkh): kPkF32, kPkHalf (dfwfm_model_pack_tables_half)
+                         // or kPkInt8 (dfwfm_model_pack_tables_int8)
   size_t pk_rows;        // rows of the copy in use
-  int32_t* d_pkovf;      // pack_tables_half: the count of values that round to +-inf
+  int32_t* d_pkovf;      // pack_tables_half / pack_tables_int8: the count of values the copy cannot serve
   int32_t npairs;
   int32_t* d_err;
   float4* d_wpack;
@@ -190,7 +192,7 @@ void dense_changed(dfwfm_model* m) {
 
 // dfwfm_model_set_tables: new tables
 void tables_changed(dfwfm_model* m) {
-  m->pkw = 0;              // the serving copy (f32 or fp16) holds the old tables' rows
+  m->pkw = 0;              // the serving copy (f32, fp16 or int8) holds the old tables' rows
   m->pkh = 0;
   m->fold_on = false;      // the folded layer 1 holds row 0 of the old numerical tables
   m->bf16fold_on = false;  // ... and so does the bf16 tower's
@@ -895,7 +897,8 @@ int dfwfm_forward_ws(dfwfm_model* m, const int64_t* xi, int64_t xi_stride, const
   rc = check_workspace(workspace, ws_bytes, split_ws_bytes(m, batch), "dfwfm_forward_workspace_bytes");
   if (rc != DFWFM_OK) return rc;
   if (m->pkh)  // its gather launch reads the plain tables: it would serve the unrounded rows
-    return fail(DFWFM_ERR_UNSUPPORTED, "the sparse deep tower does not read the fp16 serving copy");
+    return fail(DFWFM_ERR_UNSUPPORTED, m->pkh == kPkInt8 ? "the sparse deep tower does not read the int8 serving copy"
+                                                         : "the sparse deep tower does not read the fp16 serving copy");
   FwdArgs a;
   fill_forward_args(m, a, xi, xi_stride, xv, xv_stride, batch, out);
   a.part_stride = m->NC0 * 16;
@@ -1187,7 +1190,7 @@ int one_launch_forward_batches(dfwfm_model* m, const OneLaunch& v, int32_t nb, c
   return DFWFM_OK;
 }
 
-// The serving copy of the categorical tables, f32 or fp16, up to its pack launch: whether the copy covers the model
+// The serving copy of the categorical tables, f32, fp16 or int8, up to its pack launch: whether the copy covers the model
 // (a second order, first-order tables, no QR field; *covered = false: nothing else done), its rows (*rows) of `pkw`
 // floats each in the grow-only d_pkrows, the pack launch's list L and the per-field row bases for d_pk.
 int plan_serving_copy(dfwfm_model* m, int pkw, PackTabList& L, const float** bases, size_t* rows, bool* covered) {
@@ -1446,7 +1449,51 @@ int dfwfm_model_pack_tables_half(dfwfm_model* m, int32_t enable, int32_t* enable
                 "model stays on the plain tables", (unsigned)over);
   }
   m->pkw = pkw;
-  m->pkh = 1;
+  m->pkh = kPkHalf;
+  m->pk_rows = rows;
+  *enabled = 1;
+  return DFWFM_OK;
+}
+
+// The int8 serving copy (include/dfwfm_int8_tables.h): the rows of dfwfm_model_pack_tables with the second order as
+// row-wise symmetric int8 under a bf16 scale, in the same allocation.
+int dfwfm_int8_tables_abi_version(void) { return DFWFM_INT8_TABLES_ABI_VERSION; }
+
+int dfwfm_model_pack_tables_int8(dfwfm_model* m, int32_t enable, int32_t* enabled, int64_t* unservable_count,
+                                 void* stream) {
+  if (!m || !enabled) return fail(DFWFM_ERR_INVALID_ARG, "null argument");
+  *enabled = 0;
+  if (unservable_count) *unservable_count = 0;
+  m->pkw = 0;
+  m->pkh = 0;
+  if (!enable) return DFWFM_OK;
+  if (!m->tables_set) return fail(DFWFM_ERR_STATE, "set_tables must precede pack_tables_int8");
+  const int pkw = q8_row_bytes(m->D) / 4;  // the row stride, in floats as the gathers index it
+  PackTabList L;
+  const float* bases[64] = {};
+  size_t rows = 0;
+  bool covered = false;
+  const int rc = plan_serving_copy(m, pkw, L, bases, &rows, &covered);
+  if (rc != DFWFM_OK || !covered) return rc;
+  if (!m->d_pkovf) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&m->d_pkovf), sizeof(int32_t)));
+  hipStream_t s = (hipStream_t)stream;
+  // one wait for everything: `bases` is a stack buffer, and the count comes back behind the pack launch
+  int32_t bad = 0;
+  hipError_t e = hipMemcpyAsync(m->d_pk, bases, sizeof bases, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemsetAsync(m->d_pkovf, 0, sizeof(int32_t), s);
+  if (e == hipSuccess) e = launch_pack_tables_int8(L, m->d_pkovf, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(&bad, m->d_pkovf, sizeof bad, hipMemcpyDeviceToHost, s);
+  const hipError_t es = hipStreamSynchronize(s);  // also when a call above failed: `bases` may be in flight
+  if (e != hipSuccess) return hip_fail(e, "pack tables (int8) launch");
+  if (es != hipSuccess) return hip_fail(es, "pack tables (int8) synchronize");
+  if (bad != 0) {
+    if (unservable_count) *unservable_count = (int64_t)(uint32_t)bad;
+    return fail(DFWFM_ERR_UNSUPPORTED,
+                "pack_tables_int8: %u categorical second-order values are NaN, +-inf or of magnitude >= 2^127; the "
+                "model stays on the plain tables", (unsigned)bad);
+  }
+  m->pkw = pkw;
+  m->pkh = kPkInt8;
   m->pk_rows = rows;
   *enabled = 1;
   return DFWFM_OK;

@@ -135,10 +135,35 @@ __device__ __forceinline__ void load_row_fo_h(float (&v)[D], float& fo, const fl
   fo = __builtin_bit_cast(float, fw);
 }
 
+// one row of the int8 serving copy (dfwfm_model_pack_tables_int8): D bytes q (two's complement) of second order, the
+// row's bf16 scale s at the next 2-byte boundary, then the f32 first-order weight at the next dword, from a 16-byte
+// aligned row: ceil(stride / 16) dwordx4 loads (one at D = 10).  The served value float(q) * s is exact in f32 (7 bits
+// x 8 bits); an element decodes as one v_cvt_f32_i32 with a sign-extending byte select and half a packed multiply.
+template <int D>
+__device__ __forceinline__ void load_row_fo_q(float (&v)[D], float& fo, const float* __restrict__ src) {
+  constexpr int SB = q8_row_scale_byte(D);
+  constexpr int FO = q8_row_fo_word(D);
+  constexpr int NQ = FO / 4 + 1;
+  u32x4 x[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) x[q] = reinterpret_cast<const u32x4*>(src)[q];
+  const uint32_t sw = x[SB / 16][(SB / 4) % 4];
+  const float s = __builtin_bit_cast(float, (SB & 2) ? sw & 0xffff0000u : sw << 16);
+#pragma unroll
+  for (int d = 0; d < D; ++d) {
+    const uint32_t w = x[d / 16][(d / 4) % 4];
+    v[d] = (float)(int8_t)(w >> (8 * (d % 4))) * s;
+  }
+  const uint32_t fw = x[FO / 4][FO % 4];
+  fo = __builtin_bit_cast(float, fw);
+}
+
 // a row of whichever serving copy is in use (FwdArgs::pkh, wave-uniform)
 template <int D>
 __device__ __forceinline__ void load_row_pk(float (&v)[D], float& fo, const float* __restrict__ src, int pkh) {
-  if (pkh)
+  if (pkh == kPkInt8)
+    load_row_fo_q<D>(v, fo, src);
+  else if (pkh)
     load_row_fo_h<D>(v, fo, src);
   else
     load_row_fo<D>(v, fo, src);

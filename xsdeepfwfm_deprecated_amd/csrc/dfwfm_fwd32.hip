@@ -171,12 +171,13 @@ __device__ __forceinline__ void k_loop_rt(f32x4 (&acc)[RT][TPW], const float* __
 }  // namespace
 
 // QR: some field may be a QR embedding (false: no second operand, row descriptors loaded directly with the keys)
-// HT: the serving copy is the fp16 one (dfwfm_model_pack_tables_half; QR = false only): a template parameter, so that
-// the instantiations the default path runs are the code they were
-template <int D, bool QR, bool HT = false>
+// HT: the serving copy's format, FwdArgs::pkh (1: the fp16 one, dfwfm_model_pack_tables_half; 2: the int8 one,
+// dfwfm_model_pack_tables_int8; QR = false only): a template parameter, so that the instantiations the default path
+// runs are the code they were
+template <int D, bool QR, int HT = kPkF32>
 __global__ void __launch_bounds__(kNTH) __attribute__((amdgpu_waves_per_eu(4)))
 fwd32_kernel(FwdArgs p) {
-  static_assert(!HT || !QR, "the fp16 serving copy: never with QR fields");
+  static_assert(HT == kPkF32 || !QR, "the fp16 / int8 serving copy: never with QR fields");
   constexpr int RPT = (kRows * 48 + kNTH - 1) / kNTH;  // gather rows per thread: F <= 48
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x;
@@ -374,7 +375,9 @@ fwd32_kernel(FwdArgs p) {
         for (int d = 0; d < D; ++d) vb[k][d] = 0.f;
       }
       if (!QR && live[k] && pkrow[QR ? 0 : k]) {  // second and first order in one aligned row
-        if constexpr (HT)
+        if constexpr (HT == kPkInt8)
+          load_row_fo_q<D>(va[k], fa[k], pa[k]);
+        else if constexpr (HT == kPkHalf)
           load_row_fo_h<D>(va[k], fa[k], pa[k]);
         else
           load_row_fo<D>(va[k], fa[k], pa[k]);
@@ -679,7 +682,10 @@ bool fwd32_supported(int F, int D, int H, int NT, int NC0, int tailI, int NG) {
 hipError_t launch_fwd32(const FwdArgs& a, int D, size_t lds, hipStream_t s) {
   if (D != 10) return hipErrorInvalidValue;
   auto k = (a.flags & kHasQR) ? fwd32_kernel<10, true> : fwd32_kernel<10, false>;
-  if (a.pkh) k = fwd32_kernel<10, false, true>;  // (the fp16 copy is never built for a model with QR fields)
+  // (the fp16 and int8 copies are never built for a model with QR fields)
+  if (a.pkh == kPkHalf) k = fwd32_kernel<10, false, kPkHalf>;
+  else if (a.pkh == kPkInt8) k = fwd32_kernel<10, false, kPkInt8>;
+  else if (a.pkh) return hipErrorInvalidValue;
   hipError_t e = ensure_lds_limit(reinterpret_cast<const void*>(k), lds);
   if (e != hipSuccess) return e;
   const unsigned grid = fwd_grid(a, kRows);

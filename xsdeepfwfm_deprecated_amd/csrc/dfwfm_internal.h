@@ -71,7 +71,8 @@ struct FwdArgs {
   int32_t* err;
   const float* const* pk;  // dfwfm_model_pack_tables: per field, rows of pkw floats (emb2 row, emb1 weight, zero
   int32_t pkw;             // pad) for the categorical fields; pkw = 0: the plain tables (PART 3 reads it)
-  int32_t pkh;             // 1: the fp16 copy of dfwfm_model_pack_tables_half (pkw is still the row stride in floats)
+  int32_t pkh;             // the copy's format (pkw is the row stride in floats in all of them): 0 f32, 1 the fp16 copy
+                           // of dfwfm_model_pack_tables_half, 2 the int8 copy of dfwfm_model_pack_tables_int8
   const float* upack;  // FwFM A-operand fragments [MT][S][64]: strictly-upper (R + R^T)/2
   const int2* pairs;   // kPairs: the nonzero strictly-upper entries of (R + R^T)/2, (k | l << 16, w bits), k-major
   int32_t npairs;
@@ -596,6 +597,15 @@ constexpr int half_row_bytes(int D) {  // row stride: 32 B while the row fits, e
 }
 // L.pkw: the row stride in floats (half_row_bytes / 4); *overflow counts the values that round to +-inf
 hipError_t launch_pack_tables_half(const PackTabList& L, int32_t* overflow, hipStream_t s);
+// dfwfm_model_pack_tables_int8: the int8 rows [D bytes q | pad to 2 B | bf16 scale | pad to 4 B | f32 emb1 weight |
+// zero pad]
+constexpr int q8_row_scale_byte(int D) { return (D + 1) & ~1; }                     // the byte where the scale starts
+constexpr int q8_row_fo_word(int D) { return (q8_row_scale_byte(D) + 2 + 3) / 4; }  // the dword of the first-order weight
+constexpr int q8_row_bytes(int D) { return (4 * q8_row_fo_word(D) + 4 + 15) & ~15; }  // row stride: 16 B while it fits
+// L.pkw: the row stride in floats (q8_row_bytes / 4); *unservable counts the values that are NaN, +-inf or >= 2^127
+hipError_t launch_pack_tables_int8(const PackTabList& L, int32_t* unservable, hipStream_t s);
+// FwdArgs::pkh
+constexpr int kPkF32 = 0, kPkHalf = 1, kPkInt8 = 2;
 // the gather + shallow part alone (-> a.part_e / a.part_fs): the sparse deep tower's first launch
 hipError_t launch_forward_gather(const FwdArgs& a, int D, size_t lds1, hipStream_t s);
 hipError_t launch_pack_list(const PackList& L, int total_blocks, hipStream_t s);

@@ -71,9 +71,10 @@ namespace dfwfm {
 // split tail tile rides on its register sets (mlp_k_loop_s)
 // QR: some field may be a QR embedding (false: the gather carries no second operand and loads its row descriptors
 // directly -- PART 3, and PART 0's static form)
-// HT: the serving copy is the fp16 one (dfwfm_model_pack_tables_half; QR = false only).  A template parameter, not a
-// branch on p.pkh: the branch cost registers or scratch in a dozen instantiations (profiles/half_tables)
-template <int D, int TPW, int KS, bool TRAIN, int PART, int NG, int NS, bool QR = true, bool HT = false>
+// HT: the serving copy's format, FwdArgs::pkh (1: the fp16 one, dfwfm_model_pack_tables_half; 2: the int8 one,
+// dfwfm_model_pack_tables_int8; either with QR = false only).  A template parameter, not a branch on p.pkh: the branch
+// cost registers or scratch in a dozen instantiations (profiles/half_tables)
+template <int D, int TPW, int KS, bool TRAIN, int PART, int NG, int NS, bool QR = true, int HT = kPkF32>
 __global__ void __launch_bounds__(64 * NG * KS)
 __attribute__((amdgpu_waves_per_eu(PART == 1 ? 3 : (PART == 3 ? (NG == 4 ? DFWFM_P3_WPE4 : DFWFM_P3_WPE)
                                                                : (NG == 8 ? (TRAIN ? 2 : 4) : DFWFM_FWD_WPE)))))
@@ -171,7 +172,7 @@ fwd_kernel(FwdArgs p) {
   // the inference forward with the serving copy (dfwfm_model_pack_tables): a categorical row and its first-order
   // weight are ONE row of pkw floats
   constexpr bool kPackable = (PART == 3 || (PART == 0 && !TRAIN)) && !QR && kDirectDesc;
-  static_assert(!HT || kPackable, "the fp16 serving copy: an instantiation that reads the serving copy");
+  static_assert(HT == kPkF32 || kPackable, "the fp16 / int8 serving copy: an instantiation that reads the serving copy");
   bool pkrow[kPackable ? RPT : 1];
   if constexpr (kDirectDesc) {
 #pragma unroll
@@ -341,7 +342,9 @@ fwd_kernel(FwdArgs p) {
         for (int d = 0; d < D; ++d) vb[k][d] = 0.f;
       }
       if (kPackable && live[k] && pkrow[kPackable ? k : 0]) {  // second and first order in one aligned row
-        if constexpr (HT)
+        if constexpr (HT == kPkInt8)
+          load_row_fo_q<D>(va[k], fa[k], pa[k]);
+        else if constexpr (HT == kPkHalf)
           load_row_fo_h<D>(va[k], fa[k], pa[k]);
         else
           load_row_fo<D>(va[k], fa[k], pa[k]);
@@ -986,11 +989,16 @@ static hipError_t launch_fwd_t(const FwdArgs& a, size_t lds, hipStream_t s) {
   auto k = (S25 && a.ns == 25) ? ((S25D && !(a.flags & kHasQR)) ? fwd_kernel<D, TPW, KS, TRAIN, PART, NG, S25 ? 25 : 0, false>
                                                                : fwd_kernel<D, TPW, KS, TRAIN, PART, NG, S25 ? 25 : 0>)
                                : fwd_kernel<D, TPW, KS, TRAIN, PART, NG, 0>;
-  // the fp16 serving copy (a.pkh; never with QR fields): the forms that read it, static and generic
+  // the fp16 and int8 serving copies (a.pkh; never with QR fields): the forms that read them, static and generic
   if constexpr (PART == 0 && !TRAIN && KS == 1 && DFWFM_DIRECT_DESC_DEEP) {
-    if (a.pkh)
-      k = (S25 && a.ns == 25) ? fwd_kernel<D, TPW, KS, false, 0, NG, S25 ? 25 : 0, false, true>
-                              : fwd_kernel<D, TPW, KS, false, 0, NG, 0, false, true>;
+    if (a.pkh == kPkHalf)
+      k = (S25 && a.ns == 25) ? fwd_kernel<D, TPW, KS, false, 0, NG, S25 ? 25 : 0, false, kPkHalf>
+                              : fwd_kernel<D, TPW, KS, false, 0, NG, 0, false, kPkHalf>;
+    else if (a.pkh == kPkInt8)
+      k = (S25 && a.ns == 25) ? fwd_kernel<D, TPW, KS, false, 0, NG, S25 ? 25 : 0, false, kPkInt8>
+                              : fwd_kernel<D, TPW, KS, false, 0, NG, 0, false, kPkInt8>;
+    else if (a.pkh)
+      return hipErrorInvalidValue;
   } else if (a.pkh) {
     return hipErrorInvalidValue;  // this form would read the plain, unrounded tables
   }
@@ -1049,7 +1057,7 @@ static hipError_t launch_fwd_d(const FwdArgs& a, int tpw, int ks, int ng, size_t
     auto pick = [&](auto ng_, auto qr_, auto ht_) {
       constexpr int NG = decltype(ng_)::value;
       constexpr bool Q = decltype(qr_)::value;
-      constexpr bool HT = decltype(ht_)::value;
+      constexpr int HT = decltype(ht_)::value;
       return a.MT == 1 ? fwd_kernel<D, 1, 1, false, 3, NG, 1, Q, HT>
            : a.MT == 2 ? fwd_kernel<D, 1, 1, false, 3, NG, 2, Q, HT>
            : a.MT == 3 ? fwd_kernel<D, 1, 1, false, 3, NG, 3, Q, HT> : fwd_kernel<D, 1, 1, false, 3, NG, 4, Q, HT>;
@@ -1058,12 +1066,21 @@ static hipError_t launch_fwd_d(const FwdArgs& a, int tpw, int ks, int ng, size_t
     using I8 = std::integral_constant<int, 8>;
     using T = std::true_type;
     using Fl = std::false_type;
-    auto k = qr ? pick(I8{}, T{}, Fl{}) : (w8 ? pick(I8{}, Fl{}, Fl{}) : pick(I4{}, Fl{}, Fl{}));
-    if (a.pkh) {  // the fp16 serving copy (never with QR fields)
-      if constexpr (DFWFM_P3_DIRECT_DESC)
-        k = w8 ? pick(I8{}, Fl{}, T{}) : pick(I4{}, Fl{}, T{});
-      else
+    using F32 = std::integral_constant<int, kPkF32>;
+    using Hf = std::integral_constant<int, kPkHalf>;
+    using Q8 = std::integral_constant<int, kPkInt8>;
+    auto k = qr ? pick(I8{}, T{}, F32{}) : (w8 ? pick(I8{}, Fl{}, F32{}) : pick(I4{}, Fl{}, F32{}));
+    if (a.pkh) {  // the fp16 or int8 serving copy (never with QR fields)
+      if constexpr (DFWFM_P3_DIRECT_DESC) {
+        if (a.pkh == kPkHalf)
+          k = w8 ? pick(I8{}, Fl{}, Hf{}) : pick(I4{}, Fl{}, Hf{});
+        else if (a.pkh == kPkInt8)
+          k = w8 ? pick(I8{}, Fl{}, Q8{}) : pick(I4{}, Fl{}, Q8{});
+        else
+          return hipErrorInvalidValue;
+      } else {
         return hipErrorInvalidValue;
+      }
     }
     const int ng = w8 ? 8 : 4;
     const size_t lds3 = sizeof(float) * (size_t)lds_layout(a.F, D, a.MT, a.S, a.SX, a.SY, 1, 1, false, false, ng,
@@ -1180,6 +1197,62 @@ __global__ void __launch_bounds__(256) pack_tables_half_kernel(const PackTabList
 hipError_t launch_pack_tables_half(const PackTabList& L, int32_t* overflow, hipStream_t s) {
   if (L.nf <= 0 || L.blk0[L.nf] <= 0) return hipSuccess;
   hipLaunchKernelGGL(pack_tables_half_kernel, dim3(L.blk0[L.nf]), dim3(256), 0, s, L, overflow);
+  return hipGetLastError();
+}
+
+// dfwfm_model_pack_tables_int8: thread = one row of one categorical field, written as pkw / 4 16-byte stores:
+// [emb2 row as D bytes q, two's complement | zero byte when D is odd | bf16 scale | zeros to the next dword | emb1 weight (f32) |
+// zeros].  All in IEEE f32: t = max |w| / 127; the scale s is t rounded up to bf16, or 0 when t is below the smallest
+// normal (the row then serves zeros, whatever the device does with subnormals); q = rint(w / s) to nearest even,
+// clamped to +-127.  The values that are NaN, +-inf or >= 2^127 in magnitude are counted (the copy is then not used).
+__global__ void __launch_bounds__(256) pack_tables_int8_kernel(const PackTabList L, int32_t* unservable) {
+  int j = 0;
+  while (j + 1 < L.nf && (int)blockIdx.x >= L.blk0[j + 1]) ++j;  // this workgroup's field (wave-uniform)
+  const int64_t r = (int64_t)((int)blockIdx.x - L.blk0[j]) * 256 + threadIdx.x;
+  if (r >= L.n[j]) return;
+  const float* e2 = L.emb2[j] + r * L.D;
+  const float e1 = L.emb1[j][r];
+  float amax = 0.f;
+  int bad = 0;
+  for (int d = 0; d < L.D; ++d) {
+    const float a = fabsf(e2[d]);
+    bad += !(a < 0x1p127f);  // (NaN too)
+    amax = fmaxf(amax, a);
+  }
+  const float t = amax / 127.f;
+  const float s = (bad || !(t >= 0x1p-126f)) ? 0.f : __uint_as_float((__float_as_uint(t) + 0xFFFFu) & 0xFFFF0000u);
+  const int sb = q8_row_scale_byte(L.D);
+  const int fo = q8_row_fo_word(L.D);
+  u32x4* dst = reinterpret_cast<u32x4*>(L.dst[j] + r * L.pkw);
+  for (int q = 0; q < L.pkw / 4; ++q) {
+    u32x4 v;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int w = 4 * q + i;
+      uint32_t bits = 0;
+      if (w == fo) {
+        bits = __float_as_uint(e1);
+      } else if (w < fo) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          const int e = 4 * w + b;
+          if (e < L.D) {
+            const float qv = s == 0.f ? 0.f : fminf(fmaxf(rintf(e2[e] / s), -127.f), 127.f);
+            bits |= ((uint32_t)(int)qv & 0xffu) << (8 * b);
+          }
+        }
+        if (w == sb / 4) bits |= (__float_as_uint(s) >> 16) << (8 * (sb & 3));
+      }
+      v[i] = bits;
+    }
+    dst[q] = v;
+  }
+  if (bad) atomicAdd(unservable, bad);
+}
+
+hipError_t launch_pack_tables_int8(const PackTabList& L, int32_t* unservable, hipStream_t s) {
+  if (L.nf <= 0 || L.blk0[L.nf] <= 0) return hipSuccess;
+  hipLaunchKernelGGL(pack_tables_int8_kernel, dim3(L.blk0[L.nf]), dim3(256), 0, s, L, unservable);
   return hipGetLastError();
 }
 

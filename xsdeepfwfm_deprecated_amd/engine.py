@@ -180,6 +180,14 @@ class ForwardEngine:
         rounds to +-inf, raises DfwfmError and leaves the engine on the plain tables."""
         return self._sync_packed(tables, True, "fp16")
 
+    def sync_packed_int8(self, tables) -> bool:
+        """dfwfm_model_pack_tables_int8 (include/dfwfm_int8_tables.h): the serving copy with the second-order rows as
+        row-wise int8 under a bf16 scale, rebuilt as sync_packed rebuilds the f32 one (the three share one allocation
+        and one key, so changing the dtype re-packs).  There is one int8 path and no fallback: a model the copy does
+        not cover, or a value that is NaN, +-inf or >= 2^127 in magnitude, raises DfwfmError and leaves the engine on
+        the plain tables."""
+        return self._sync_packed(tables, True, "int8")
+
     def _sync_packed(self, tables, enable, dtype):
         key = (bool(enable), dtype) + tuple((t.data_ptr(), t._version) for pair in tables for t in pair
                                             if t is not None)
@@ -200,6 +208,18 @@ class ForwardEngine:
                 raise _lib.DfwfmError("table_dtype='fp16': the serving copy does not cover this model (it needs a "
                                       "second order, first-order tables and no QR field); its forward would read the "
                                       "unrounded f32 tables")
+        elif dtype == "int8":
+            bad = ctypes.c_int64(0)
+            rc = _lib.lib().dfwfm_model_pack_tables_int8(self.handle, 1, ctypes.byref(en), ctypes.byref(bad),
+                                                         _stream_handle(self.device))
+            if rc != _lib.DFWFM_OK and bad.value:
+                raise _lib.DfwfmError(f"table_dtype='int8': {bad.value} categorical second-order value(s) are NaN, "
+                                      "+-inf or of magnitude >= 2^127; the int8 serving copy is not built")
+            _lib.check(rc, "dfwfm_model_pack_tables_int8")
+            if not en.value:
+                raise _lib.DfwfmError("table_dtype='int8': the serving copy does not cover this model (it needs a "
+                                      "second order, first-order tables and no QR field); its forward would read the "
+                                      "unquantized f32 tables")
         else:
             _lib.check(_lib.lib().dfwfm_model_pack_tables(self.handle, int(bool(enable)), ctypes.byref(en),
                                                           _stream_handle(self.device)), "dfwfm_model_pack_tables")
@@ -212,7 +232,7 @@ class ForwardEngine:
         return self._packed_on
 
     def serving_copy_bytes(self) -> int:
-        """dfwfm_model_serving_copy_bytes: the bytes of the serving copy in use (f32 or fp16), 0 on the plain tables."""
+        """dfwfm_model_serving_copy_bytes: the bytes of the serving copy in use (f32, fp16 or int8), 0 on the plain tables."""
         n = ctypes.c_int64(0)
         _lib.check(_lib.lib().dfwfm_model_serving_copy_bytes(self.handle, ctypes.byref(n)),
                    "dfwfm_model_serving_copy_bytes")
