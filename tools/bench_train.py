@@ -1,6 +1,7 @@
 """Training-step benchmark (BASELINE.json configs[4]: DeepFwFM training, DP over RCCL).
 
     python tools/bench_train.py [--gpus N] [--steps K] [--warmup W] [--batch 4096] [--first-order lw|fwlw]
+                                [--lr-schedule 1:1e-4,2000:1e-3,200000:1e-4]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 tools/bench_train.py
 
 One step = the reference's fit() inner loop body (model/DeepFMs.py:619-637) on a resident synthetic
@@ -51,9 +52,22 @@ def main():
     ap.add_argument("--lazy-adam", action="store_true",
                     help="fused, one rank: the categorical tables' Adam over the rows each batch touched only "
                          "(FusedTrainStep(lazy_table_adam=True); not the reference's dense semantics)")
+    ap.add_argument("--lr-schedule", default=None, metavar="STEP:LR[,STEP:LR...]",
+                    help="fused: the learning rate from a piecewise-linear schedule evaluated on the device every step "
+                         "(FusedTrainStep(lr_schedule=...), e.g. \"1:1e-4,2000:1e-3,200000:1e-4\") instead of the "
+                         "fixed 1e-3 baked into the graphs")
     ap.add_argument("--gpus", type=int, default=1, help="ranks (one process per GPU; started here unless "
                                                            "torchrun already set WORLD_SIZE)")
     a = ap.parse_args()
+    schedule = None
+    if a.lr_schedule is not None:
+        from xsdeepfwfm_deprecated_amd.cli import parse_lr_schedule
+        try:
+            schedule = parse_lr_schedule(a.lr_schedule)
+        except argparse.ArgumentTypeError as e:
+            ap.error(str(e))
+        if a.mode != "fused":
+            ap.error("--lr-schedule needs --mode fused")
     from xsdeepfwfm_deprecated_amd.launch import spawn_ranks
     rc = spawn_ranks(a.gpus)  # before any HIP call
     if rc is not None:
@@ -99,7 +113,7 @@ def main():
         # the four resident batches are read in place (one captured graph set each), like a loader's ring of
         # device input buffers; --copy-inputs copies each batch into the step's own buffers first
         trainer = FusedTrainStep(model, B, lr=1e-3, weight_decay=3e-7, dist=dist, resident_inputs=not a.copy_inputs,
-                                 deterministic=not a.atomic, lazy_table_adam=a.lazy_adam)
+                                 deterministic=not a.atomic, lazy_table_adam=a.lazy_adam, lr_schedule=schedule)
 
     def step(i):
         xi, xv, y = batches[i % 4]
@@ -149,6 +163,7 @@ def main():
            "host_enqueue_us_per_step": round(host * 1e6 / a.steps, 1),
            "mode": a.mode, "deterministic": not a.atomic, "steps_per_graph": K, "inputs": "copied" if (a.copy_inputs or a.mode != "fused") else "resident (read in place)",
            "lazy_adam": bool(trainer is not None and getattr(trainer, "lazy", False)),
+           "lr_schedule": schedule,
            "final_loss_sum": round(float(loss.item()), 4)}
     if res["lazy_adam"]:
         # distinct rows the four resident batches touch per step, per table family (what the lazy step updates)

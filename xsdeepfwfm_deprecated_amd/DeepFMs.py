@@ -160,6 +160,11 @@ class DeepFMs(nn.Module):
         # Adam, so the training goldens do not cover it.  Off by default; fit() raises ValueError when it is set and
         # the fused step is not the path (a CPU module, another optimizer, a teacher model, fused_fit off)
         self.lazy_table_adam = False
+        # fit()'s fused Adam step takes its learning rate from a piecewise-linear schedule evaluated on the device at
+        # every step (FusedTrainStep(lr_schedule=[(step, lr), ...]), include/dfwfm_lr_schedule.h): warm-up and decay
+        # inside the graph-replayed step; learning_rate is then unused.  None by default: the fixed learning_rate.
+        # fit() raises ValueError when it is set and the fused step is not the path, as for lazy_table_adam
+        self.lr_schedule = None
         self._defer_index_check = 0     # >0 inside a batched caller: one flag read at its end, not per batch
         self._engine = None
 

@@ -45,7 +45,8 @@ HEADERS = ["dfwfm_internal.h", "dfwfm_device.h", "dfwfm_fused_stage.h", "dfwfm_a
            os.path.join("..", "..", "include", "dfwfm_bf16_fold.h"), os.path.join("..", "..", "include", "dfwfm_int8.h"),
            os.path.join("..", "..", "include", "dfwfm_lazy_adam.h"),
            os.path.join("..", "..", "include", "dfwfm_half_tables.h"),
-           os.path.join("..", "..", "include", "dfwfm_int8_tables.h")]
+           os.path.join("..", "..", "include", "dfwfm_int8_tables.h"),
+           os.path.join("..", "..", "include", "dfwfm_lr_schedule.h")]
 ARCH = os.environ.get("DFWFM_OFFLOAD_ARCH", "gfx950")
 CPU_PATH = os.path.join(PKG_DIR, "libdfwfm_cpu.so")
 CPU_SOURCES = ["dfwfm_cpu.cpp"]
@@ -61,6 +62,8 @@ BWD_TABLES, BWD_MLP_WEIGHTS, BWD_TILES, BWD_SPREAD, BWD_REDUCE, BWD_SCATTER = 1,
 FAMILY_SECOND, FAMILY_FIRST = 0, 1  # dfwfm_sparse_grads_local
 LAZY_PLAIN, LAZY_QUOTIENT, LAZY_REMAINDER = 0, 1, 2  # dfwfm_lazy_adam_table.kind
 ADAM_STATE_BYTES = 48
+LR_MAX_KNOTS = 64  # dfwfm_lr_schedule.h
+LR_SCHEDULE_BYTES = 16 + 16 * LR_MAX_KNOTS
 
 
 class DfwfmError(RuntimeError):
@@ -105,6 +108,10 @@ class dfwfm_lazy_adam_table(ctypes.Structure):
                 ("exp_avg_sq", ctypes.c_void_p), ("stamp", ctypes.c_void_p), ("rows", ctypes.c_int64),
                 ("key_range", ctypes.c_int64), ("c", ctypes.c_int64), ("width", ctypes.c_int32),
                 ("column", ctypes.c_int32), ("kind", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class dfwfm_lr_knot(ctypes.Structure):
+    _fields_ = [("step", ctypes.c_int64), ("lr", ctypes.c_double)]
 
 
 class dfwfm_sparse_dest(ctypes.Structure):
@@ -245,6 +252,39 @@ INT8_TABLES_SIGNATURES = {
     "dfwfm_model_pack_tables_int8": (ctypes.c_int, [_P, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
                                                     ctypes.POINTER(ctypes.c_int64), _P]),
 }
+
+# device-resident learning-rate schedules for the graph-replayable Adam steps (include/dfwfm_lr_schedule.h): same
+# library, its own header and ABI version
+LR_SCHEDULE_SIGNATURES = {
+    "dfwfm_lr_schedule_abi_version": (ctypes.c_int, []),
+    "dfwfm_lr_schedule_eval": (ctypes.c_int, [ctypes.POINTER(dfwfm_lr_knot), ctypes.c_int32, ctypes.c_int64,
+                                              ctypes.POINTER(ctypes.c_double)]),
+    "dfwfm_lr_schedule_write": (ctypes.c_int, [_P, ctypes.POINTER(dfwfm_lr_knot), ctypes.c_int32, _P]),
+    "dfwfm_adam_step_dev_sched": (ctypes.c_int, [ctypes.POINTER(dfwfm_adam_tensor), ctypes.c_int32, _P,
+                                                 ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                                 _P, _P]),
+    "dfwfm_lazy_adam_step_dev_sched": (ctypes.c_int, [ctypes.POINTER(dfwfm_lazy_adam_table), ctypes.c_int32, _P,
+                                                      ctypes.c_int64, ctypes.c_int64, _P, ctypes.c_double,
+                                                      ctypes.c_double, ctypes.c_double, ctypes.c_double, _P, _P]),
+}
+
+
+def lr_knots(schedule):
+    """A ctypes array of dfwfm_lr_knot from [(step, lr), ...] (at least one element long, for an empty list)."""
+    pairs = [(int(s), float(v)) for s, v in schedule]
+    arr = (dfwfm_lr_knot * max(len(pairs), 1))()
+    for i, (s, v) in enumerate(pairs):
+        arr[i] = dfwfm_lr_knot(s, v)
+    return arr, len(pairs)
+
+
+def lr_schedule_eval(schedule, step):
+    """The schedule's value at `step` on the host (dfwfm_lr_schedule_eval: the bits the kernels compute)."""
+    arr, n = lr_knots(schedule)
+    out = ctypes.c_double(0.0)
+    check(lib().dfwfm_lr_schedule_eval(arr, n, int(step), ctypes.byref(out)), "dfwfm_lr_schedule_eval")
+    return out.value
+
 
 _lib = None
 _lock = threading.Lock()
@@ -493,6 +533,12 @@ def lib():
             fn.argtypes = args
         if L.dfwfm_int8_tables_abi_version() != 1:
             raise DfwfmError("libdfwfm int8 tables ABI mismatch")
+        for name, (res, args) in LR_SCHEDULE_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        if L.dfwfm_lr_schedule_abi_version() != 1:
+            raise DfwfmError("libdfwfm lr schedule ABI mismatch")
         _lib = L
     return _lib
 

@@ -13,6 +13,28 @@ import torch
 from .DeepFMs import DeepFMs
 
 
+def parse_lr_schedule(spec):
+    """"1:1e-4,2000:1e-3,200000:1e-4" -> [(1, 1e-4), (2000, 1e-3), (200000, 1e-4)]: the (step, lr) knots of
+    FusedTrainStep(lr_schedule=...) under the rules of include/dfwfm_lr_schedule.h (1 to 64 knots, integer steps
+    strictly increasing from >= 1, every lr finite and >= 0).  An argparse type: a malformed spec is a usage error."""
+    import math
+    knots = []
+    for part in spec.split(","):
+        try:
+            step, lr = part.split(":")
+            knots.append((int(step.strip()), float(lr)))
+        except ValueError:
+            raise argparse.ArgumentTypeError(f"lr schedule knot {part!r} is not STEP:LR") from None
+    if not 1 <= len(knots) <= 64:
+        raise argparse.ArgumentTypeError(f"an lr schedule has 1 to 64 knots, not {len(knots)}")
+    for i, (step, lr) in enumerate(knots):
+        if step < 1 or (i and step <= knots[i - 1][0]):
+            raise argparse.ArgumentTypeError("lr schedule steps must be strictly increasing from >= 1")
+        if not (math.isfinite(lr) and lr >= 0):
+            raise argparse.ArgumentTypeError(f"lr schedule rate {lr!r} is not finite and >= 0")
+    return knots
+
+
 def get_parser():
     """utils/parameters.py:2-51 (flags, defaults and help as the reference) + -data_root."""
     p = argparse.ArgumentParser(description="Hyperparameter tuning and selection")
@@ -84,6 +106,11 @@ def get_parser():
       help="training on a HIP device with Adam: the categorical tables' Adam updates only the rows each batch touched "
            "(DeepFMs.lazy_table_adam; SparseAdam / LazyAdam semantics, NOT the reference's dense Adam: untouched rows "
            "get no moment decay and no L2)")
+    a("-lr_schedule", default=None, type=parse_lr_schedule, metavar="STEP:LR[,STEP:LR...]",
+      help="training on a HIP device with Adam: a piecewise-linear learning-rate schedule evaluated on the device "
+           "inside the graph-replayed step, e.g. \"1:1e-4,2000:1e-3,200000:1e-4\" for a warm-up and a decay "
+           "(DeepFMs.lr_schedule; steps count Adam steps from 1, constant before the first and after the last knot; "
+           "-learning_rate is then unused)")
     return p
 
 
@@ -136,4 +163,5 @@ def get_model(cuda, feature_sizes, pars, dynamic_quantization=False, static_quan
     m.bf16_fold = bool(getattr(pars, "bf16_fold", 0))
     m.table_dtype = getattr(pars, "table_dtype", "f32")  # a CPU model with "fp16" or "int8" raises at its first forward
     m.lazy_table_adam = bool(getattr(pars, "lazy_adam", 0))  # fit() raises if the fused Adam step is not the path
+    m.lr_schedule = getattr(pars, "lr_schedule", None)  # fit() raises if the fused Adam step is not the path
     return m

@@ -54,6 +54,31 @@ __device__ __forceinline__ AdamCoef adam_coef(int64_t step, const AdamHyper& h) 
                   (float)h.wd, (float)sqrt(bc2)};
 }
 
+// A device-resident learning-rate schedule's value at step s (include/dfwfm_lr_schedule.h: the contract), by the 64
+// lanes of one wave, all of which call this and get the value.  Lane k loads knot k (the block always holds kLrKnots
+// of them, so the load needs no count first); these loads, the count's and the caller's load of the step counter do
+// not depend on one another and are in flight together: the schedule adds no memory round trip to the head of a
+// launch's workgroups, where a search by one thread would add five or six.  The lane that holds the segment (or the
+// end) evaluates it -- lr_segment, the host's own function -- and the wave reads its result.  The cases exclude one
+// another in a valid table, in the contract's order; a block that was never written yields some knot's lr, no fault.
+__device__ __forceinline__ double lr_schedule_value(const LrSchedule* __restrict__ sd, int64_t s) {
+  const int lane = threadIdx.x & 63;
+  const int n = sd->n;
+  const LrKnot a = sd->k[lane];
+  const int64_t step_j = (int64_t)__shfl_down((long long)a.step, 1);  // knot lane + 1 (lane 63: its own, unused)
+  const double lr_j = __shfl_down(a.lr, 1);
+  // (the three cases as flags formed ahead of any branch: with the count first used inside a branch the compiler
+  // sinks its load there, behind the wait for the knots -- the dependent round trip this layout is there to avoid)
+  const bool first = (lane == 0) & (s <= a.step);
+  const bool last = (lane == n - 1) & (s >= a.step);
+  const bool seg = (lane + 1 < n) & (a.step <= s) & (s < step_j) & !first;
+  const bool hit = first | last | seg;
+  double v = a.lr;
+  if (seg) v = lr_segment(a.step, a.lr, step_j, lr_j, s);
+  const unsigned long long hits = __ballot(hit);
+  return __shfl(v, hits ? __ffsll(hits) - 1 : 0);
+}
+
 // the last workgroup of a step's last launch (ticket == nwg - 1): record the step's scalars and advance the counter
 __device__ __forceinline__ void adam_advance(AdamDevState* __restrict__ st, const AdamCoef& c, int64_t step) {
   st->step_size = c.step_size;

@@ -19,6 +19,7 @@
 #include "../../include/dfwfm_int8.h"
 #include "../../include/dfwfm_fold.h"
 #include "../../include/dfwfm_lazy_adam.h"
+#include "../../include/dfwfm_lr_schedule.h"
 #include "../../include/dfwfm_half_tables.h"
 #include "../../include/dfwfm_int8_tables.h"
 
@@ -2182,8 +2183,9 @@ int dfwfm_set_step_source(dfwfm_model* m, const int64_t* step_dev) {
   return DFWFM_OK;
 }
 
-int dfwfm_adam_step_dev(const dfwfm_adam_tensor* t, int32_t n, double lr, double beta1, double beta2, double eps,
-                        double weight_decay, void* state_dev, void* stream) {
+// dfwfm_adam_step_dev, and with a schedule block (sched != null: `lr` unused) dfwfm_adam_step_dev_sched
+static int adam_step_dev_impl(const dfwfm_adam_tensor* t, int32_t n, double lr, const LrSchedule* sched, double beta1,
+                              double beta2, double eps, double weight_decay, void* state_dev, void* stream) {
   if ((n > 0 && !t) || !state_dev) return fail(DFWFM_ERR_INVALID_ARG, "null argument");
   if (n < 0) return fail(DFWFM_ERR_INVALID_ARG, "negative tensor count");
   static_assert(sizeof(AdamDevState) == DFWFM_ADAM_STATE_BYTES, "state block size");
@@ -2203,7 +2205,8 @@ int dfwfm_adam_step_dev(const dfwfm_adam_tensor* t, int32_t n, double lr, double
     const int64_t nb = last ? 0 : (t[keep[k]].numel + kAdamBlock - 1) / kAdamBlock;
     if (nb > 0x7fffffff) return fail(DFWFM_ERR_UNSUPPORTED, "adam tensor %d too large", keep[k]);
     if (list.n > 0 && (last || list.n == kAdamList || blocks + nb > 0x7fffffff)) {
-      hipError_t e = launch_adam_dev(list, (int)blocks, st, h, last, (hipStream_t)stream);
+      hipError_t e = sched ? launch_adam_dev_sched(list, (int)blocks, st, h, last, sched, (hipStream_t)stream)
+                           : launch_adam_dev(list, (int)blocks, st, h, last, (hipStream_t)stream);
       if (e != hipSuccess) return hip_fail(e, "adam launch");
       list.n = 0;
       blocks = 0;
@@ -2212,17 +2215,24 @@ int dfwfm_adam_step_dev(const dfwfm_adam_tensor* t, int32_t n, double lr, double
     adam_push(list, blocks, t[keep[k]], nb);
   }
   if (keep.empty()) {
-    hipError_t e = launch_adam_dev(list, 1, st, h, true, (hipStream_t)stream);
+    hipError_t e = sched ? launch_adam_dev_sched(list, 1, st, h, true, sched, (hipStream_t)stream)
+                         : launch_adam_dev(list, 1, st, h, true, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "adam launch");
   }
   return DFWFM_OK;
 }
 
+int dfwfm_adam_step_dev(const dfwfm_adam_tensor* t, int32_t n, double lr, double beta1, double beta2, double eps,
+                        double weight_decay, void* state_dev, void* stream) {
+  return adam_step_dev_impl(t, n, lr, nullptr, beta1, beta2, eps, weight_decay, state_dev, stream);
+}
+
 int dfwfm_lazy_adam_abi_version(void) { return DFWFM_LAZY_ADAM_ABI_VERSION; }
 
-int dfwfm_lazy_adam_step_dev(const dfwfm_lazy_adam_table* t, int32_t n, const int64_t* xi, int64_t xi_stride,
-                             int64_t batch, double lr, double beta1, double beta2, double eps, double weight_decay,
-                             void* state_dev, void* stream) {
+// dfwfm_lazy_adam_step_dev, and with a schedule block (sched != null: `lr` unused) dfwfm_lazy_adam_step_dev_sched
+static int lazy_adam_step_dev_impl(const dfwfm_lazy_adam_table* t, int32_t n, const int64_t* xi, int64_t xi_stride,
+                                   int64_t batch, double lr, const LrSchedule* sched, double beta1, double beta2,
+                                   double eps, double weight_decay, void* state_dev, void* stream) {
   if (!state_dev) return fail(DFWFM_ERR_INVALID_ARG, "null state block");
   if (n < 0) return fail(DFWFM_ERR_INVALID_ARG, "negative table count");
   if (batch < 0) return fail(DFWFM_ERR_INVALID_ARG, "negative batch");
@@ -2267,7 +2277,8 @@ int dfwfm_lazy_adam_step_dev(const dfwfm_lazy_adam_table* t, int32_t n, const in
     if (last || list.n == kLazyList || blocks + nb > 0x7fffffff) {
       a.bump = last ? 1 : 0;
       a.nblocks = (int32_t)blocks;
-      hipError_t e = launch_lazy_adam(list, a, (hipStream_t)stream);
+      hipError_t e = sched ? launch_lazy_adam_sched(list, a, sched, (hipStream_t)stream)
+                           : launch_lazy_adam(list, a, (hipStream_t)stream);
       if (e != hipSuccess) return hip_fail(e, "lazy adam launch");
       list.n = 0;
       blocks = 0;
@@ -2290,6 +2301,76 @@ int dfwfm_lazy_adam_step_dev(const dfwfm_lazy_adam_table* t, int32_t n, const in
     blocks += nb;
   }
   return DFWFM_OK;
+}
+
+int dfwfm_lazy_adam_step_dev(const dfwfm_lazy_adam_table* t, int32_t n, const int64_t* xi, int64_t xi_stride,
+                             int64_t batch, double lr, double beta1, double beta2, double eps, double weight_decay,
+                             void* state_dev, void* stream) {
+  return lazy_adam_step_dev_impl(t, n, xi, xi_stride, batch, lr, nullptr, beta1, beta2, eps, weight_decay, state_dev,
+                                 stream);
+}
+
+// ---------------------------------------------------------------- include/dfwfm_lr_schedule.h
+int dfwfm_lr_schedule_abi_version(void) { return DFWFM_LR_SCHEDULE_ABI_VERSION; }
+
+// the table's checks, shared by the host evaluation and the rewrite
+static int lr_knots_check(const dfwfm_lr_knot* k, int32_t n) {
+  if (!k) return fail(DFWFM_ERR_INVALID_ARG, "null knot array");
+  if (n < 1 || n > DFWFM_LR_MAX_KNOTS)
+    return fail(DFWFM_ERR_INVALID_ARG, "%d knots: a schedule has 1 to %d", n, DFWFM_LR_MAX_KNOTS);
+  if (k[0].step < 1) return fail(DFWFM_ERR_INVALID_ARG, "first step %lld below 1", (long long)k[0].step);
+  for (int i = 0; i < n; ++i) {
+    if (i > 0 && k[i].step <= k[i - 1].step)
+      return fail(DFWFM_ERR_INVALID_ARG, "knot %d: steps not strictly increasing (%lld after %lld)", i,
+                  (long long)k[i].step, (long long)k[i - 1].step);
+    if (!(k[i].lr >= 0.0) || std::isinf(k[i].lr))  // (NaN fails the comparison)
+      return fail(DFWFM_ERR_INVALID_ARG, "knot %d: lr %g is NaN, infinite or negative", i, k[i].lr);
+  }
+  return DFWFM_OK;
+}
+
+int dfwfm_lr_schedule_eval(const dfwfm_lr_knot* knots, int32_t n, int64_t step, double* lr) {
+  if (!lr) return fail(DFWFM_ERR_INVALID_ARG, "null result pointer");
+  if (int rc = lr_knots_check(knots, n)) return rc;
+  if (step <= knots[0].step) {
+    *lr = knots[0].lr;
+  } else if (step >= knots[n - 1].step) {
+    *lr = knots[n - 1].lr;
+  } else {
+    int i = 0;
+    while (knots[i + 1].step <= step) ++i;  // step[i] <= step < step[i+1]
+    *lr = lr_segment(knots[i].step, knots[i].lr, knots[i + 1].step, knots[i + 1].lr, step);
+  }
+  return DFWFM_OK;
+}
+
+int dfwfm_lr_schedule_write(void* sched_dev, const dfwfm_lr_knot* knots, int32_t n, void* stream) {
+  if (!sched_dev) return fail(DFWFM_ERR_INVALID_ARG, "null schedule block");
+  if (int rc = lr_knots_check(knots, n)) return rc;
+  static_assert(sizeof(LrSchedule) == DFWFM_LR_SCHEDULE_BYTES && sizeof(LrKnot) == sizeof(dfwfm_lr_knot) &&
+                    kLrKnots == DFWFM_LR_MAX_KNOTS,
+                "schedule block layout");
+  LrSchedule k;
+  memset(&k, 0, sizeof k);
+  k.n = n;
+  for (int i = 0; i < n; ++i) k.k[i] = LrKnot{knots[i].step, knots[i].lr};
+  hipError_t e = launch_lr_schedule_write(reinterpret_cast<LrSchedule*>(sched_dev), k, (hipStream_t)stream);
+  return e == hipSuccess ? DFWFM_OK : hip_fail(e, "lr schedule write");
+}
+
+int dfwfm_adam_step_dev_sched(const dfwfm_adam_tensor* t, int32_t n, const void* sched_dev, double beta1, double beta2,
+                              double eps, double weight_decay, void* state_dev, void* stream) {
+  if (!sched_dev) return fail(DFWFM_ERR_INVALID_ARG, "null schedule block");
+  return adam_step_dev_impl(t, n, 0.0, reinterpret_cast<const LrSchedule*>(sched_dev), beta1, beta2, eps, weight_decay,
+                            state_dev, stream);
+}
+
+int dfwfm_lazy_adam_step_dev_sched(const dfwfm_lazy_adam_table* t, int32_t n, const int64_t* xi, int64_t xi_stride,
+                                   int64_t batch, const void* sched_dev, double beta1, double beta2, double eps,
+                                   double weight_decay, void* state_dev, void* stream) {
+  if (!sched_dev) return fail(DFWFM_ERR_INVALID_ARG, "null schedule block");
+  return lazy_adam_step_dev_impl(t, n, xi, xi_stride, batch, 0.0, reinterpret_cast<const LrSchedule*>(sched_dev), beta1,
+                                 beta2, eps, weight_decay, state_dev, stream);
 }
 
 int dfwfm_bce_grad(const float* z, const float* y, int64_t n, double denom, float* dz, float* loss_sum,

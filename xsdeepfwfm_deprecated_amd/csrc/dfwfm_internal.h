@@ -1,6 +1,7 @@
 // dfwfm_internal.h -- types shared by the kernels and the C-ABI layer.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
@@ -709,5 +710,34 @@ inline int64_t lazy_blocks(int width, int64_t batch) {
 }
 // one launch; with `bump` (the call's last launch) the last workgroup to finish advances the counter
 hipError_t launch_lazy_adam(const LazyList& list, const LazyArgs& a, hipStream_t s);
+
+// Device-resident learning-rate schedules (include/dfwfm_lr_schedule.h: the contract).  The device block, and the
+// same knots as the kernel argument of the rewrite launch.
+constexpr int kLrKnots = 64;  // DFWFM_LR_MAX_KNOTS: one knot per lane of a wave
+struct LrKnot {
+  int64_t step;
+  double lr;
+};
+struct LrSchedule {
+  int32_t n;
+  int32_t pad[3];
+  LrKnot k[kLrKnots];
+};
+static_assert(sizeof(LrSchedule) == 16 + 16 * kLrKnots, "schedule block layout");
+static_assert(sizeof(LazyList) + sizeof(LazyArgs) + sizeof(const LrSchedule*) + 64 <= 4096,
+              "scheduled lazy Adam launch arguments over 4 KiB");
+// one segment of a schedule at step[i] <= s < step[i+1], every rounding fixed: the host's dfwfm_lr_schedule_eval and
+// the kernels share it (fma is std::fma on the host and one v_fma_f64 on the device: it cannot be split)
+__host__ __device__ inline double lr_segment(int64_t step_i, double lr_i, int64_t step_j, double lr_j, int64_t s) {
+  const double t = (double)(s - step_i) / (double)(step_j - step_i);
+  return fma(lr_j - lr_i, t, lr_i);
+}
+// the scheduled twins of launch_adam_dev / launch_lazy_adam: lr of `h` is ignored, the rate is sched's value at
+// (counter + 1)
+hipError_t launch_adam_dev_sched(const AdamList& list, int total_blocks, AdamDevState* st, const AdamHyper& h,
+                                 bool bump, const LrSchedule* sched, hipStream_t s);
+hipError_t launch_lazy_adam_sched(const LazyList& list, const LazyArgs& a, const LrSchedule* sched, hipStream_t s);
+// the block's rewrite: one 64-lane launch, the knots as kernel arguments (k.n knots, the rest zero-filled)
+hipError_t launch_lr_schedule_write(LrSchedule* dst, const LrSchedule& k, hipStream_t s);
 
 }  // namespace dfwfm

@@ -25,12 +25,27 @@ __device__ __forceinline__ int32_t lazy_stamp(int64_t step) {
   return (int32_t)(uint32_t)((uint64_t)(step - 1) % 0xffffffffull + 1ull);
 }
 
-__global__ void __launch_bounds__(256) lazy_adam_kernel(const LazyList list, const LazyArgs a) {
+// SCHED: the rate is a device-resident schedule's value at counter + 1 (include/dfwfm_lr_schedule.h), evaluated by
+// the first wave (lr_schedule_value, dfwfm_adam.h) and put in the place of a.h.lr; nothing else differs.
+template <bool SCHED>
+__device__ __forceinline__ void lazy_adam_body(const LazyList& list, const LazyArgs& a,
+                                               const LrSchedule* __restrict__ sched) {
   __shared__ AdamCoef sc;
   __shared__ int64_t s_step;
-  if (threadIdx.x == 0) {
-    s_step = a.st->step + 1;
-    sc = adam_coef(s_step, a.h);
+  if constexpr (SCHED) {
+    if (threadIdx.x < 64) {
+      const int64_t step = a.st->step + 1;
+      const double lr = lr_schedule_value(sched, step);
+      if (threadIdx.x == 0) {
+        s_step = step;
+        sc = adam_coef(step, AdamHyper{lr, a.h.b1, a.h.b2, a.h.eps, a.h.wd});
+      }
+    }
+  } else {
+    if (threadIdx.x == 0) {
+      s_step = a.st->step + 1;
+      sc = adam_coef(s_step, a.h);
+    }
   }
   __syncthreads();
   const AdamCoef c = sc;
@@ -98,6 +113,22 @@ __global__ void __launch_bounds__(256) lazy_adam_kernel(const LazyList list, con
     __syncthreads();  // s_rows is rewritten by the next work block
   }
   if (a.bump && threadIdx.x == 0 && atomicAdd(&a.st->ticket, 1) == (int)gridDim.x - 1) adam_advance(a.st, sc, s_step);
+}
+
+__global__ void __launch_bounds__(256) lazy_adam_kernel(const LazyList list, const LazyArgs a) {
+  lazy_adam_body<false>(list, a, nullptr);
+}
+
+__global__ void __launch_bounds__(256) lazy_adam_sched_kernel(const LazyList list, const LazyArgs a,
+                                                              const LrSchedule* __restrict__ sched) {
+  lazy_adam_body<true>(list, a, sched);
+}
+
+hipError_t launch_lazy_adam_sched(const LazyList& list, const LazyArgs& a, const LrSchedule* sched, hipStream_t s) {
+  const int total = a.nblocks < 1 ? 1 : a.nblocks;  // as launch_lazy_adam
+  const int grid = total < kAdamGrid ? total : kAdamGrid;
+  hipLaunchKernelGGL(lazy_adam_sched_kernel, dim3(grid), dim3(256), 0, s, list, a, sched);
+  return hipGetLastError();
 }
 
 hipError_t launch_lazy_adam(const LazyList& list, const LazyArgs& a, hipStream_t s) {

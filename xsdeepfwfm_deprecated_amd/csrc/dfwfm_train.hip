@@ -1723,6 +1723,35 @@ __global__ void __launch_bounds__(256) adam_dev_kernel(const AdamList list, Adam
   adam_dev_part(list, st, h, bump, nblocks, blockIdx.x, gridDim.x);
 }
 
+// adam_dev_kernel with the rate read from a device-resident schedule (include/dfwfm_lr_schedule.h): the first wave
+// evaluates the schedule at counter + 1 (lr_schedule_value, dfwfm_adam.h) and its lane 0 forms adam_coef with that
+// double in the place of h.lr; everything after the barrier is adam_dev_part's.
+__global__ void __launch_bounds__(256) adam_dev_sched_kernel(const AdamList list, AdamDevState* __restrict__ st,
+                                                             const AdamHyper h, int bump, int nblocks,
+                                                             const LrSchedule* __restrict__ sched) {
+  __shared__ AdamCoef sc;
+  __shared__ int64_t s_step;
+  if (threadIdx.x < 64) {
+    const int64_t step = st->step + 1;
+    const double lr = lr_schedule_value(sched, step);
+    if (threadIdx.x == 0) {
+      s_step = step;
+      sc = adam_coef(step, AdamHyper{lr, h.b1, h.b2, h.eps, h.wd});
+    }
+  }
+  __syncthreads();
+  const int nwg = gridDim.x;
+  for (int b = blockIdx.x; b < nblocks; b += nwg) adam_block<kAdamFuseG>(list, sc, b);
+  if (bump && threadIdx.x == 0 && atomicAdd(&st->ticket, 1) == nwg - 1) adam_advance(st, sc, s_step);
+}
+
+// dfwfm_lr_schedule_write: one wave, lane k stores knot k of the kernel argument (the host zero-filled the knots past
+// the count), lane 0 the count
+__global__ void __launch_bounds__(64) lr_schedule_write_kernel(LrSchedule* __restrict__ dst, const LrSchedule k) {
+  dst->k[threadIdx.x] = k.k[threadIdx.x];
+  if (threadIdx.x == 0) dst->n = k.n;
+}
+
 // dL/dz of BCE-with-logits with the loss normalised by `denom` (torch: (sigmoid(z) - y) * 1, then
 // divided by numel for reduction='mean'); optionally the loss sum (stable form) into *loss_sum.
 __global__ void __launch_bounds__(256) bce_grad_kernel(const float* __restrict__ z, const float* __restrict__ y,
@@ -1917,6 +1946,20 @@ hipError_t launch_adam_dev(const AdamList& list, int total_blocks, AdamDevState*
   if (total_blocks <= 0) return hipSuccess;
   const int grid = total_blocks < kAdamGrid ? total_blocks : kAdamGrid;
   hipLaunchKernelGGL(adam_dev_kernel, dim3(grid), dim3(256), 0, s, list, st, h, bump ? 1 : 0, total_blocks);
+  return hipGetLastError();
+}
+
+hipError_t launch_adam_dev_sched(const AdamList& list, int total_blocks, AdamDevState* st, const AdamHyper& h,
+                                 bool bump, const LrSchedule* sched, hipStream_t s) {
+  if (total_blocks <= 0) return hipSuccess;
+  const int grid = total_blocks < kAdamGrid ? total_blocks : kAdamGrid;
+  hipLaunchKernelGGL(adam_dev_sched_kernel, dim3(grid), dim3(256), 0, s, list, st, h, bump ? 1 : 0, total_blocks,
+                     sched);
+  return hipGetLastError();
+}
+
+hipError_t launch_lr_schedule_write(LrSchedule* dst, const LrSchedule& k, hipStream_t s) {
+  hipLaunchKernelGGL(lr_schedule_write_kernel, dim3(1), dim3(kLrKnots), 0, s, dst, k);
   return hipGetLastError();
 }
 

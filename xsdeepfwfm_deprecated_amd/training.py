@@ -185,11 +185,19 @@ class FusedTrainStep:
     dfwfm_lazy_adam.h: torch.optim.SparseAdam / LazyAdam semantics -- an untouched row gets no moment decay and no
     L2 that step, which is NOT the reference's dense Adam), and the tables' region of the gradient buffer is no longer
     filled every step: the lazy call zeroes the rows it updates, which are the rows the scatter wrote.  Everything
-    that is not a categorical table stays on the dense Adam.  One process only."""
+    that is not a categorical table stays on the dense Adam.  One process only.
+
+    lr_schedule: a list of (step, lr) knots (include/dfwfm_lr_schedule.h: piecewise linear, constant before the first
+    and after the last knot; at most 64 knots, steps strictly increasing from >= 1).  The knots live in a device block
+    of the trainer's, written once here; every Adam kernel evaluates the table at the step it is about to take (its
+    state block's counter + 1) instead of taking ``lr`` as a kernel argument, so one captured graph serves every rate:
+    warm-up and decay run inside graph replays and step_many, and set_lr() / set_lr_schedule() rewrite the block
+    between steps without a recapture.  ``lr`` is then unused.  Replicas under data parallelism evaluate the same
+    table at the same step and stay bit-identical.  None (the default): the rate is ``lr``, fixed, as before."""
 
     def __init__(self, model, batch_size, lr=1e-3, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8,
                  use_graph=True, dist=None, sparse_exchange=True, resident_inputs=False, max_graph_sets=8,
-                 max_many_sets=2, deterministic=None, lazy_table_adam=False):
+                 max_many_sets=2, deterministic=None, lazy_table_adam=False, lr_schedule=None):
         dev = model._device()
         if dev.type != "cuda":
             raise _lib.DfwfmError("FusedTrainStep runs only on a HIP device")
@@ -250,6 +258,12 @@ class FusedTrainStep:
         # one process: the categorical tables' Adam runs on the scatter's side stream right behind it (its own
         # counter, state_t), beside the weight-gradient GEMM; everything else on `state` after the GEMM
         self.state_t = torch.zeros_like(self.state)
+        # lr_schedule: the knots' device block, read by every Adam kernel of this trainer (state, state_b and state_t
+        # advance in lockstep, so all of them evaluate it at the same step)
+        self.lr_schedule, self.sched = None, None
+        if lr_schedule is not None:
+            self.sched = torch.zeros(_lib.LR_SCHEDULE_BYTES // 8, dtype=torch.int64, device=dev)
+            self.set_lr_schedule(lr_schedule)
         views = {}
         adam = (_lib.dfwfm_adam_tensor * len(params))()
         for i, p in enumerate(params):
@@ -412,6 +426,12 @@ class FusedTrainStep:
             return
         b1, b2 = self.betas
         xi = self._in[0]
+        if self.sched is not None:
+            _lib.check(self.L.dfwfm_lazy_adam_step_dev_sched(
+                self.lazy_tables, self.n_cat, ctypes.c_void_p(xi.data_ptr()), xi.stride(0), n,
+                ctypes.c_void_p(self.sched.data_ptr()), b1, b2, self.eps, self.wd,
+                ctypes.c_void_p(self.state_t.data_ptr()), self._stream()), "dfwfm_lazy_adam_step_dev_sched")
+            return
         _lib.check(self.L.dfwfm_lazy_adam_step_dev(self.lazy_tables, self.n_cat, ctypes.c_void_p(xi.data_ptr()),
                                                    xi.stride(0), n, self.lr, b1, b2, self.eps, self.wd,
                                                    ctypes.c_void_p(self.state_t.data_ptr()), self._stream()),
@@ -498,27 +518,52 @@ class FusedTrainStep:
         s.wait_stream(s1)
 
     def _adam_range(self, tensors, n, state):
+        """The dense Adam of n tensors on one state block: the rate a kernel argument, or with lr_schedule read from
+        the trainer's schedule block when the kernels run."""
         b1, b2 = self.betas
+        if self.sched is not None:
+            _lib.check(self.L.dfwfm_adam_step_dev_sched(tensors, n, ctypes.c_void_p(self.sched.data_ptr()), b1, b2,
+                                                        self.eps, self.wd, ctypes.c_void_p(state.data_ptr()),
+                                                        self._stream()), "dfwfm_adam_step_dev_sched")
+            return
         _lib.check(self.L.dfwfm_adam_step_dev(tensors, n, self.lr, b1, b2, self.eps, self.wd,
                                               ctypes.c_void_p(state.data_ptr()), self._stream()),
                    "dfwfm_adam_step_dev")
+
+    def set_lr_schedule(self, schedule):
+        """Rewrite the schedule block with the knots [(step, lr), ...] on the current stream (one tiny launch, no
+        synchronisation): the next step, eager or a graph replay, evaluates the new table -- no recapture.  Only on a
+        trainer built with lr_schedule."""
+        if self.sched is None:
+            raise RuntimeError("FusedTrainStep was built without lr_schedule: its rate is a kernel argument baked into "
+                               "the captured graphs")
+        knots = [(int(s), float(v)) for s, v in schedule]
+        arr, n = _lib.lr_knots(knots)
+        _lib.check(self.L.dfwfm_lr_schedule_write(ctypes.c_void_p(self.sched.data_ptr()), arr, n, self._stream()),
+                   "dfwfm_lr_schedule_write")
+        self.lr_schedule = knots
+
+    def set_lr(self, lr):
+        """A rate chosen on the host (a drop on a validation plateau): the schedule becomes the single knot (1, lr)."""
+        self.set_lr_schedule([(1, lr)])
+
+    def lr_at(self, step):
+        """The rate of step `step` (1-based) on the host: dfwfm_lr_schedule_eval, the bits the kernels compute; without
+        a schedule, the fixed rate."""
+        if self.sched is None:
+            return self.lr
+        return _lib.lr_schedule_eval(self.lr_schedule, step)
 
     def _bucketed(self):
         return self.dist is not None and self.n_bucket_a < self.grad.numel()
 
     def _adam_main(self):
-        b1, b2 = self.betas
         if self.n_main:
-            _lib.check(self.L.dfwfm_adam_step_dev(self.adam, self.n_main, self.lr, b1, b2, self.eps, self.wd,
-                                                  ctypes.c_void_p(self.state.data_ptr()), self._stream()),
-                       "dfwfm_adam_step_dev")
+            self._adam_range(self.adam, self.n_main, self.state)
 
     def _adam_mlp(self):
-        b1, b2 = self.betas
         if self.n_adam > self.n_main:
-            _lib.check(self.L.dfwfm_adam_step_dev(self.adam_mlp, self.n_adam - self.n_main, self.lr, b1, b2, self.eps,
-                                                  self.wd, ctypes.c_void_p(self.state_b.data_ptr()), self._stream()),
-                       "dfwfm_adam_step_dev")
+            self._adam_range(self.adam_mlp, self.n_adam - self.n_main, self.state_b)
 
     def _part2(self, n=None):
         if self.split_adam:  # the tables (state_t) then the rest (state): both counters bumped every step
@@ -533,10 +578,7 @@ class FusedTrainStep:
 
     def _adam_all(self):
         """Every tensor's Adam in one launch (one step counter, `state`): one process without categorical tables."""
-        b1, b2 = self.betas
-        _lib.check(self.L.dfwfm_adam_step_dev(self.adam, self.n_adam, self.lr, b1, b2, self.eps, self.wd,
-                                              ctypes.c_void_p(self.state.data_ptr()), self._stream()),
-                   "dfwfm_adam_step_dev")
+        self._adam_range(self.adam, self.n_adam, self.state)
 
     def _exchange(self, run_part1b, run_apply=None):
         """Data parallelism: all-reduce the gradient buffer (RCCL).  Bucketed: the first bucket (every
@@ -1022,8 +1064,13 @@ def fit(model, Xi_train, Xv_train, y_train, Xi_valid=None, Xv_valid=None, y_vali
         # never train silently with another optimizer's semantics: the lazy update exists on the fused step only
         raise ValueError("lazy_table_adam needs the fused training step: a module on a HIP device, "
                          "optimizer_type='adam', no teacher model and fused_fit on")
+    sched = getattr(model, "lr_schedule", None)
+    if sched is not None and not fused:
+        # never train silently at another rate: the schedule exists on the fused step only
+        raise ValueError("lr_schedule needs the fused training step: a module on a HIP device, "
+                         "optimizer_type='adam', no teacher model and fused_fit on")
     trainer = FusedTrainStep(model, bs, lr=model.learning_rate, weight_decay=model.weight_decay,
-                             dist=dist, lazy_table_adam=lazy) if fused else None
+                             dist=dist, lazy_table_adam=lazy, lr_schedule=sched) if fused else None
     try:
         return _fit_loop(model, trainer, dist, rank, world, Xi_train, Xv_train, y_train, x_size, ncat, is_valid,
                          Xi_valid if is_valid else None, Xv_valid if is_valid else None,
