@@ -2,6 +2,7 @@
 
     python tools/bench_train.py [--gpus N] [--steps K] [--warmup W] [--batch 4096] [--first-order lw|fwlw]
                                 [--lr-schedule 1:1e-4,2000:1e-3,200000:1e-4]
+                                [--optimizer adam|sgd|adag|rmsp] [--momentum M]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 tools/bench_train.py
 
 One step = the reference's fit() inner loop body (model/DeepFMs.py:619-637) on a resident synthetic
@@ -56,6 +57,10 @@ def main():
                     help="fused: the learning rate from a piecewise-linear schedule evaluated on the device every step "
                          "(FusedTrainStep(lr_schedule=...), e.g. \"1:1e-4,2000:1e-3,200000:1e-4\") instead of the "
                          "fixed 1e-3 baked into the graphs")
+    ap.add_argument("--optimizer", choices=["adam", "sgd", "adag", "rmsp"], default="adam",
+                    help="fused: FusedTrainStep(optimizer=...) (include/dfwfm_optim.h); autograd: torch.optim.SGD / "
+                         "Adagrad / RMSprop as the reference constructs them (adam: the HIP Adam)")
+    ap.add_argument("--momentum", type=float, default=0.0, help="--optimizer sgd: the momentum")
     ap.add_argument("--gpus", type=int, default=1, help="ranks (one process per GPU; started here unless "
                                                            "torchrun already set WORLD_SIZE)")
     a = ap.parse_args()
@@ -98,7 +103,14 @@ def main():
     params = synth.synth_state(shapes, 39, 10, 400, True, True, seed=1234)
     model.load_state_dict({k: torch.from_numpy(v) for k, v in params.items()})
     model = model.to(dev).train()
-    opt = Adam(model.parameters(), lr=1e-3, weight_decay=3e-7)
+    if a.optimizer == "adam":
+        opt = Adam(model.parameters(), lr=1e-3, weight_decay=3e-7)
+    elif a.mode != "fused":  # the autograd path's optimizers (training.make_optimizer)
+        opt = {"sgd": lambda ps: torch.optim.SGD(ps, lr=1e-3, momentum=a.momentum, weight_decay=3e-7),
+               "adag": lambda ps: torch.optim.Adagrad(ps, lr=1e-3, weight_decay=3e-7),
+               "rmsp": lambda ps: torch.optim.RMSprop(ps, lr=1e-3, weight_decay=3e-7)}[a.optimizer](model.parameters())
+    # bytes an update moves per parameter: parameter read + written, gradient read, each state array read + written
+    opt_bytes = 28 if a.optimizer == "adam" else (12 if (a.optimizer == "sgd" and a.momentum == 0.0) else 20)
     B = a.batch
     batches = []
     for i in range(4):
@@ -113,7 +125,8 @@ def main():
         # the four resident batches are read in place (one captured graph set each), like a loader's ring of
         # device input buffers; --copy-inputs copies each batch into the step's own buffers first
         trainer = FusedTrainStep(model, B, lr=1e-3, weight_decay=3e-7, dist=dist, resident_inputs=not a.copy_inputs,
-                                 deterministic=not a.atomic, lazy_table_adam=a.lazy_adam, lr_schedule=schedule)
+                                 deterministic=not a.atomic, lazy_table_adam=a.lazy_adam, lr_schedule=schedule,
+                                 **({} if a.optimizer == "adam" else dict(optimizer=a.optimizer, momentum=a.momentum)))
 
     def step(i):
         xi, xv, y = batches[i % 4]
@@ -156,14 +169,16 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         ms = float(t.item())
         torch.distributed.barrier()
-    res = {"metric": "DeepFwFM training samples/sec (Criteo-39, Adam, dropout 0.5)",
+    opt_name = {"adam": "Adam", "sgd": "SGD", "adag": "Adagrad", "rmsp": "RMSprop"}[a.optimizer]
+    res = {"metric": f"DeepFwFM training samples/sec (Criteo-39, {opt_name}, dropout 0.5)",
            "value": round(world * B * a.steps / (ms / 1e3), 1), "unit": "samples/s", "n_gpus": world,
            "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms / a.steps, 4), "per_gpu_batch": B,
            "first_order": a.first_order, "dropout": not a.no_dropout, "wall_s": round(wall, 3),
            "host_enqueue_us_per_step": round(host * 1e6 / a.steps, 1),
            "mode": a.mode, "deterministic": not a.atomic, "steps_per_graph": K, "inputs": "copied" if (a.copy_inputs or a.mode != "fused") else "resident (read in place)",
            "lazy_adam": bool(trainer is not None and getattr(trainer, "lazy", False)),
-           "lr_schedule": schedule,
+           "lr_schedule": schedule, "optimizer": a.optimizer, "momentum": a.momentum,
+           "optimizer_bytes_per_param": opt_bytes,
            "final_loss_sum": round(float(loss.item()), 4)}
     if res["lazy_adam"]:
         # distinct rows the four resident batches touch per step, per table family (what the lazy step updates)

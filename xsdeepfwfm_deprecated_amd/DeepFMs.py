@@ -165,6 +165,12 @@ class DeepFMs(nn.Module):
         # inside the graph-replayed step; learning_rate is then unused.  None by default: the fixed learning_rate.
         # fit() raises ValueError when it is set and the fused step is not the path, as for lazy_table_adam
         self.lr_schedule = None
+        # fit() runs optimizer_type 'sgd' / 'adag' / 'rmsp' on the graph-replayed fused step as well
+        # (FusedTrainStep(optimizer=...), include/dfwfm_optim.h: torch.optim.SGD / Adagrad / RMSprop as the reference
+        # constructs them) instead of autograd + torch.optim, and lr_schedule then works with them.  Off by default:
+        # those optimizers stay on the autograd path.  fit() raises ValueError when it is set and the fused step is
+        # not the path (a CPU module, a teacher model, fused_fit off), as for lazy_table_adam
+        self.fused_optimizer = False
         self._defer_index_check = 0     # >0 inside a batched caller: one flag read at its end, not per batch
         self._engine = None
 

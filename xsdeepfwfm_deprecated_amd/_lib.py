@@ -25,6 +25,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libdfwfm.so")
 LOAD_PATH = os.path.join(PKG_DIR, os.environ["DFWFM_LIB"]) if os.environ.get("DFWFM_LIB") else LIB_PATH
 SOURCES = ["dfwfm_kernels.hip", "dfwfm_fwd32.hip", "dfwfm_ftrain.hip", "dfwfm_train.hip", "dfwfm_prune.hip", "dfwfm_metrics.hip", "dfwfm_sparse.hip",
            "dfwfm_spmlp.hip", "dfwfm_serve.hip", "dfwfm_bf16.hip", "dfwfm_bf16_fused.hip", "dfwfm_int8.hip", "dfwfm_lazy_adam.hip",
+           "dfwfm_optim.hip",
            "dfwfm_capi.hip"]
 # the forward / backward kernel templates are instantiated once per embedding size, each size in its own
 # translation unit (-DDFWFM_KD=<D>) so they compile in parallel; the plain object holds everything else
@@ -38,7 +39,7 @@ def _units():
     for s in PER_D_SOURCES:
         u += [(s, f"{os.path.splitext(s)[0]}_d{d}.o", [f"-DDFWFM_KD={d}"]) for d in EMB_SIZES]
     return u
-HEADERS = ["dfwfm_internal.h", "dfwfm_device.h", "dfwfm_fused_stage.h", "dfwfm_adam.h",
+HEADERS = ["dfwfm_internal.h", "dfwfm_device.h", "dfwfm_fused_stage.h", "dfwfm_adam.h", "dfwfm_optim.h",
            os.path.join("..", "..", "include", "dfwfm.h"),
            os.path.join("..", "..", "include", "dfwfm_serve.h"), os.path.join("..", "..", "include", "dfwfm_bf16.h"),
            os.path.join("..", "..", "include", "dfwfm_bf16_fused.h"), os.path.join("..", "..", "include", "dfwfm_fold.h"),
@@ -46,7 +47,8 @@ HEADERS = ["dfwfm_internal.h", "dfwfm_device.h", "dfwfm_fused_stage.h", "dfwfm_a
            os.path.join("..", "..", "include", "dfwfm_lazy_adam.h"),
            os.path.join("..", "..", "include", "dfwfm_half_tables.h"),
            os.path.join("..", "..", "include", "dfwfm_int8_tables.h"),
-           os.path.join("..", "..", "include", "dfwfm_lr_schedule.h")]
+           os.path.join("..", "..", "include", "dfwfm_lr_schedule.h"),
+           os.path.join("..", "..", "include", "dfwfm_optim.h")]
 ARCH = os.environ.get("DFWFM_OFFLOAD_ARCH", "gfx950")
 CPU_PATH = os.path.join(PKG_DIR, "libdfwfm_cpu.so")
 CPU_SOURCES = ["dfwfm_cpu.cpp"]
@@ -64,6 +66,7 @@ LAZY_PLAIN, LAZY_QUOTIENT, LAZY_REMAINDER = 0, 1, 2  # dfwfm_lazy_adam_table.kin
 ADAM_STATE_BYTES = 48
 LR_MAX_KNOTS = 64  # dfwfm_lr_schedule.h
 LR_SCHEDULE_BYTES = 16 + 16 * LR_MAX_KNOTS
+OPTIM_SGD, OPTIM_ADAGRAD, OPTIM_RMSPROP = 0, 1, 2  # dfwfm_optim_kind
 
 
 class DfwfmError(RuntimeError):
@@ -112,6 +115,17 @@ class dfwfm_lazy_adam_table(ctypes.Structure):
 
 class dfwfm_lr_knot(ctypes.Structure):
     _fields_ = [("step", ctypes.c_int64), ("lr", ctypes.c_double)]
+
+
+class dfwfm_optim_tensor(ctypes.Structure):
+    _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("state", ctypes.c_void_p),
+                ("numel", ctypes.c_int64)]
+
+
+class dfwfm_optim_hyper(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int32), ("reserved", ctypes.c_int32), ("lr", ctypes.c_double),
+                ("weight_decay", ctypes.c_double), ("momentum", ctypes.c_double), ("alpha", ctypes.c_double),
+                ("eps", ctypes.c_double)]
 
 
 class dfwfm_sparse_dest(ctypes.Structure):
@@ -267,6 +281,25 @@ LR_SCHEDULE_SIGNATURES = {
                                                       ctypes.c_int64, ctypes.c_int64, _P, ctypes.c_double,
                                                       ctypes.c_double, ctypes.c_double, ctypes.c_double, _P, _P]),
 }
+
+# the SGD, Adagrad and RMSprop steps of the fused training step (include/dfwfm_optim.h): same library, its own header
+# and ABI version
+OPTIM_SIGNATURES = {
+    "dfwfm_optim_abi_version": (ctypes.c_int, []),
+    "dfwfm_optim_step": (ctypes.c_int, [ctypes.POINTER(dfwfm_optim_tensor), ctypes.c_int32,
+                                        ctypes.POINTER(dfwfm_optim_hyper), ctypes.c_int64, _P]),
+    "dfwfm_optim_step_dev": (ctypes.c_int, [ctypes.POINTER(dfwfm_optim_tensor), ctypes.c_int32,
+                                            ctypes.POINTER(dfwfm_optim_hyper), _P, _P]),
+    "dfwfm_optim_step_dev_sched": (ctypes.c_int, [ctypes.POINTER(dfwfm_optim_tensor), ctypes.c_int32,
+                                                  ctypes.POINTER(dfwfm_optim_hyper), _P, _P, _P]),
+    "dfwfm_optim_elem_ref": (ctypes.c_int, [ctypes.POINTER(dfwfm_optim_hyper), ctypes.c_int64,
+                                            ctypes.POINTER(ctypes.c_float), ctypes.c_float,
+                                            ctypes.POINTER(ctypes.c_float)]),
+}
+# FusedTrainStep's optimizer names (the reference's optimizer_type values) -> (kind, default eps, needs a state array
+# whatever the momentum)
+OPTIM_KINDS = {"sgd": (OPTIM_SGD, 0.0, False), "adag": (OPTIM_ADAGRAD, 1e-10, True),
+               "rmsp": (OPTIM_RMSPROP, 1e-8, True)}
 
 
 def lr_knots(schedule):
@@ -539,6 +572,12 @@ def lib():
             fn.argtypes = args
         if L.dfwfm_lr_schedule_abi_version() != 1:
             raise DfwfmError("libdfwfm lr schedule ABI mismatch")
+        for name, (res, args) in OPTIM_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        if L.dfwfm_optim_abi_version() != 1:
+            raise DfwfmError("libdfwfm optim ABI mismatch")
         _lib = L
     return _lib
 

@@ -111,6 +111,10 @@ def get_parser():
            "inside the graph-replayed step, e.g. \"1:1e-4,2000:1e-3,200000:1e-4\" for a warm-up and a decay "
            "(DeepFMs.lr_schedule; steps count Adam steps from 1, constant before the first and after the last knot; "
            "-learning_rate is then unused)")
+    a("-fused_optimizer", default=0, type=int, choices=[0, 1],
+      help="training on a HIP device: optimizer_type 'sgd', 'adag' and 'rmsp' run on the graph-replayed fused step too "
+           "(DeepFMs.fused_optimizer, include/dfwfm_optim.h) instead of autograd + torch.optim; fit() raises when the "
+           "fused step is not the path")
     return p
 
 
@@ -164,4 +168,5 @@ def get_model(cuda, feature_sizes, pars, dynamic_quantization=False, static_quan
     m.table_dtype = getattr(pars, "table_dtype", "f32")  # a CPU model with "fp16" or "int8" raises at its first forward
     m.lazy_table_adam = bool(getattr(pars, "lazy_adam", 0))  # fit() raises if the fused Adam step is not the path
     m.lr_schedule = getattr(pars, "lr_schedule", None)  # fit() raises if the fused Adam step is not the path
+    m.fused_optimizer = bool(getattr(pars, "fused_optimizer", 0))  # fit() raises if the fused step is not the path
     return m

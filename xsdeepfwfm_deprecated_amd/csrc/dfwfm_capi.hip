@@ -22,6 +22,8 @@
 #include "../../include/dfwfm_lr_schedule.h"
 #include "../../include/dfwfm_half_tables.h"
 #include "../../include/dfwfm_int8_tables.h"
+#include "../../include/dfwfm_optim.h"
+#include "dfwfm_optim.h"
 
 using namespace dfwfm;
 
@@ -2371,6 +2373,122 @@ int dfwfm_lazy_adam_step_dev_sched(const dfwfm_lazy_adam_table* t, int32_t n, co
   if (!sched_dev) return fail(DFWFM_ERR_INVALID_ARG, "null schedule block");
   return lazy_adam_step_dev_impl(t, n, xi, xi_stride, batch, 0.0, reinterpret_cast<const LrSchedule*>(sched_dev), beta1,
                                  beta2, eps, weight_decay, state_dev, stream);
+}
+
+// ---------------------------------------------------------------- include/dfwfm_optim.h
+int dfwfm_optim_abi_version(void) { return DFWFM_OPTIM_ABI_VERSION; }
+
+// the hyper-parameters' checks (lr is not read by a scheduled call) and the kernels' kind
+static int optim_hyper_check(const dfwfm_optim_hyper* h, bool with_lr, int* kind) {
+  if (!h) return fail(DFWFM_ERR_INVALID_ARG, "null hyper-parameters");
+  if (h->kind != DFWFM_OPTIM_SGD && h->kind != DFWFM_OPTIM_ADAGRAD && h->kind != DFWFM_OPTIM_RMSPROP)
+    return fail(DFWFM_ERR_INVALID_ARG, "unknown optimizer kind %d", h->kind);
+  const struct {
+    const char* name;
+    double v;
+    bool on;
+  } hp[] = {{"lr", h->lr, with_lr}, {"weight_decay", h->weight_decay, true}, {"momentum", h->momentum, true},
+            {"alpha", h->alpha, true}, {"eps", h->eps, true}};
+  for (const auto& x : hp)
+    if (x.on && (!(x.v >= 0.0) || std::isinf(x.v)))  // (NaN fails the comparison)
+      return fail(DFWFM_ERR_INVALID_ARG, "%s %g is NaN, infinite or negative", x.name, x.v);
+  if (!(h->alpha < 1.0)) return fail(DFWFM_ERR_INVALID_ARG, "alpha %g outside [0, 1)", h->alpha);
+  *kind = h->kind == DFWFM_OPTIM_ADAGRAD ? kOptAdagrad
+          : h->kind == DFWFM_OPTIM_RMSPROP ? kOptRmsprop
+          : (h->momentum != 0.0 ? kOptSgdMom : kOptSgd);
+  return DFWFM_OK;
+}
+
+// dfwfm_optim_step (st null: the host's step number), dfwfm_optim_step_dev and, with a schedule block,
+// dfwfm_optim_step_dev_sched
+static int optim_step_impl(const dfwfm_optim_tensor* t, int32_t n, const dfwfm_optim_hyper* hyper, int64_t step,
+                           AdamDevState* st, const LrSchedule* sched, void* stream) {
+  int kind = 0;
+  if (int rc = optim_hyper_check(hyper, sched == nullptr, &kind)) return rc;
+  if (n < 0) return fail(DFWFM_ERR_INVALID_ARG, "negative tensor count");
+  if (n > 0 && !t) return fail(DFWFM_ERR_INVALID_ARG, "null tensor array");
+  std::vector<int> keep;
+  for (int i = 0; i < n; ++i) {
+    if (!t[i].grad || t[i].numel <= 0) continue;
+    if (!t[i].param) return fail(DFWFM_ERR_INVALID_ARG, "optim tensor %d: null param", i);
+    if (kind != kOptSgd && !t[i].state) return fail(DFWFM_ERR_INVALID_ARG, "optim tensor %d: null state pointer", i);
+    if ((t[i].numel + kAdamBlock - 1) / kAdamBlock > 0x7fffffff)
+      return fail(DFWFM_ERR_UNSUPPORTED, "optim tensor %d too large", i);
+    keep.push_back(i);
+  }
+  OptimArgs a;
+  memset(&a, 0, sizeof a);
+  a.st = st;
+  a.sched = sched;
+  a.h = OptimHyper{hyper->lr, hyper->weight_decay, hyper->momentum, hyper->alpha, hyper->eps};
+  a.step = step;
+  // the tensors' launches (<= kOptimList tensors each); with a state block the last one advances its step counter (a
+  // list without tensors still advances it: one empty workgroup)
+  OptimList list;
+  memset(&list, 0, sizeof list);
+  int64_t blocks = 0;
+  for (size_t k = 0; k <= keep.size(); ++k) {
+    const bool last = k == keep.size();
+    const int64_t nb = last ? 0 : (t[keep[k]].numel + kAdamBlock - 1) / kAdamBlock;
+    if (list.n > 0 && (last || list.n == kOptimList || blocks + nb > 0x7fffffff)) {
+      a.bump = (last && st) ? 1 : 0;
+      a.nblocks = (int32_t)blocks;
+      hipError_t e = launch_optim(kind, list, a, (hipStream_t)stream);
+      if (e != hipSuccess) return hip_fail(e, "optim launch");
+      list.n = 0;
+      blocks = 0;
+    }
+    if (last) break;
+    const dfwfm_optim_tensor& x = t[keep[k]];
+    list.t[list.n] = OptimTensor{x.param, x.grad, kind == kOptSgd ? nullptr : x.state, x.numel};
+    list.block0[list.n++] = (int32_t)blocks;
+    blocks += nb;
+  }
+  if (keep.empty() && st) {
+    a.bump = 1;
+    a.nblocks = 0;
+    hipError_t e = launch_optim(kind, list, a, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "optim launch");
+  }
+  return DFWFM_OK;
+}
+
+int dfwfm_optim_step(const dfwfm_optim_tensor* t, int32_t n, const dfwfm_optim_hyper* hyper, int64_t step,
+                     void* stream) {
+  if (step < 1) return fail(DFWFM_ERR_INVALID_ARG, "step %lld below 1", (long long)step);
+  return optim_step_impl(t, n, hyper, step, nullptr, nullptr, stream);
+}
+
+int dfwfm_optim_step_dev(const dfwfm_optim_tensor* t, int32_t n, const dfwfm_optim_hyper* hyper, void* state_dev,
+                         void* stream) {
+  if (!state_dev) return fail(DFWFM_ERR_INVALID_ARG, "null state block");
+  return optim_step_impl(t, n, hyper, 0, reinterpret_cast<AdamDevState*>(state_dev), nullptr, stream);
+}
+
+int dfwfm_optim_step_dev_sched(const dfwfm_optim_tensor* t, int32_t n, const dfwfm_optim_hyper* hyper,
+                               const void* sched_dev, void* state_dev, void* stream) {
+  if (!state_dev) return fail(DFWFM_ERR_INVALID_ARG, "null state block");
+  if (!sched_dev) return fail(DFWFM_ERR_INVALID_ARG, "null schedule block");
+  return optim_step_impl(t, n, hyper, 0, reinterpret_cast<AdamDevState*>(state_dev),
+                         reinterpret_cast<const LrSchedule*>(sched_dev), stream);
+}
+
+int dfwfm_optim_elem_ref(const dfwfm_optim_hyper* hyper, int64_t step, float* p, float g, float* state) {
+  int kind = 0;
+  if (int rc = optim_hyper_check(hyper, true, &kind)) return rc;
+  if (step < 1) return fail(DFWFM_ERR_INVALID_ARG, "step %lld below 1", (long long)step);
+  if (!p) return fail(DFWFM_ERR_INVALID_ARG, "null param");
+  if (kind != kOptSgd && !state) return fail(DFWFM_ERR_INVALID_ARG, "null state pointer");
+  const OptimCoef c = optim_coef(
+      step, OptimHyper{hyper->lr, hyper->weight_decay, hyper->momentum, hyper->alpha, hyper->eps}, hyper->lr);
+  float none = 0.f;  // plain SGD's state: never read
+  switch (kind) {
+    case kOptSgd: optim_elem<kOptSgd>(c, *p, g, none); break;
+    case kOptSgdMom: optim_elem<kOptSgdMom>(c, *p, g, *state); break;
+    case kOptAdagrad: optim_elem<kOptAdagrad>(c, *p, g, *state); break;
+    default: optim_elem<kOptRmsprop>(c, *p, g, *state); break;
+  }
+  return DFWFM_OK;
 }
 
 int dfwfm_bce_grad(const float* z, const float* y, int64_t n, double denom, float* dz, float* loss_sum,

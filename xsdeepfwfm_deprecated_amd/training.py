@@ -193,11 +193,21 @@ class FusedTrainStep:
     state block's counter + 1) instead of taking ``lr`` as a kernel argument, so one captured graph serves every rate:
     warm-up and decay run inside graph replays and step_many, and set_lr() / set_lr_schedule() rewrite the block
     between steps without a recapture.  ``lr`` is then unused.  Replicas under data parallelism evaluate the same
-    table at the same step and stay bit-identical.  None (the default): the rate is ``lr``, fixed, as before."""
+    table at the same step and stay bit-identical.  None (the default): the rate is ``lr``, fixed, as before.
 
-    def __init__(self, model, batch_size, lr=1e-3, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8,
+    optimizer: "adam" (the default: everything above, unchanged), or the reference's other optimizer_type values on
+    the same step (include/dfwfm_optim.h) -- "sgd" (torch.optim.SGD(lr, momentum, weight_decay)), "adag"
+    (torch.optim.Adagrad(lr, weight_decay, eps)), "rmsp" (torch.optim.RMSprop(lr, alpha, eps, weight_decay)).  Every
+    place that runs Adam runs the chosen update instead, on the same state blocks: eager steps, the captured graphs,
+    step_many, resident inputs, data parallelism, lr_schedule.  The state is ONE flat buffer (``opt_state``: momentum
+    buffer, sum or square_avg, laid out like the gradient buffer) and none at all for SGD with momentum == 0;
+    ``exp_avg`` / ``exp_avg_sq`` are then None.  ``eps`` None: the kind's default (Adam and RMSprop 1e-8, Adagrad
+    1e-10).  lazy_table_adam is Adam's: with another optimizer it raises ValueError."""
+
+    def __init__(self, model, batch_size, lr=1e-3, weight_decay=0.0, betas=(0.9, 0.999), eps=None,
                  use_graph=True, dist=None, sparse_exchange=True, resident_inputs=False, max_graph_sets=8,
-                 max_many_sets=2, deterministic=None, lazy_table_adam=False, lr_schedule=None):
+                 max_many_sets=2, deterministic=None, lazy_table_adam=False, lr_schedule=None,
+                 optimizer="adam", momentum=0.0, alpha=0.99):
         dev = model._device()
         if dev.type != "cuda":
             raise _lib.DfwfmError("FusedTrainStep runs only on a HIP device")
@@ -205,9 +215,18 @@ class FusedTrainStep:
             # the touched set of a data-parallel step is the union of every rank's exchanged lists
             raise NotImplementedError("lazy_table_adam under data parallelism: the touched rows are the union of the "
                                       "ranks' exchanged lists, which the lazy step does not read yet")
+        if optimizer != "adam" and optimizer not in _lib.OPTIM_KINDS:
+            raise ValueError(f"optimizer {optimizer!r}: one of 'adam', 'sgd', 'adag', 'rmsp'")
+        if optimizer != "adam" and lazy_table_adam:
+            raise ValueError("lazy_table_adam is Adam's row-lazy step: it does not combine with optimizer="
+                             f"{optimizer!r}")
         self.model, self.dev = model, dev
         self.B = int(batch_size)
+        self.optimizer = optimizer
+        if eps is None:
+            eps = 1e-8 if optimizer == "adam" else _lib.OPTIM_KINDS[optimizer][1]
         self.lr, self.wd, self.betas, self.eps = float(lr), float(weight_decay), tuple(betas), float(eps)
+        self.momentum, self.alpha = float(momentum), float(alpha)
         self.dist = dist
         self.use_graph = use_graph
         self.resident_inputs = bool(resident_inputs)
@@ -247,8 +266,13 @@ class FusedTrainStep:
         self.n_bucket_a = next((offs[i] for i, p in enumerate(params) if id(p) in mlp_ids), total)
         self.sparse = dist is not None and bool(sparse_exchange) and self.n_tables > 0
         self.grad = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.exp_avg = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.exp_avg_sq = torch.zeros(total, dtype=torch.float32, device=dev)
+        self.exp_avg = self.exp_avg_sq = self.opt_state = None
+        if optimizer == "adam":
+            self.exp_avg = torch.zeros(total, dtype=torch.float32, device=dev)
+            self.exp_avg_sq = torch.zeros(total, dtype=torch.float32, device=dev)
+        elif _lib.OPTIM_KINDS[optimizer][2] or self.momentum != 0.0:
+            # the kind's one state array (momentum buffer, sum, square_avg); plain SGD has none
+            self.opt_state = torch.zeros(total, dtype=torch.float32, device=dev)
         self.state = torch.zeros(_lib.ADAM_STATE_BYTES // 8, dtype=torch.int64, device=dev)
         # under data parallelism Adam runs as two launches -- everything but the MLP
         # (state), the MLP weights and biases (state_b) -- so that the first can overlap the weight-gradient GEMM;
@@ -265,20 +289,32 @@ class FusedTrainStep:
             self.sched = torch.zeros(_lib.LR_SCHEDULE_BYTES // 8, dtype=torch.int64, device=dev)
             self.set_lr_schedule(lr_schedule)
         views = {}
-        adam = (_lib.dfwfm_adam_tensor * len(params))()
+        # the optimizer's tensor list: dfwfm_adam_tensor, or with another optimizer dfwfm_optim_tensor (the same
+        # order and sub-lists; _adam_range hands them to the chosen optimizer's entry point)
+        tensor_t = _lib.dfwfm_adam_tensor if optimizer == "adam" else _lib.dfwfm_optim_tensor
+        adam = (tensor_t * len(params))()
         for i, p in enumerate(params):
             n, off = p.numel(), offs[i]
-            g, m, v = (t[off:off + n].view_as(p) for t in (self.grad, self.exp_avg, self.exp_avg_sq))
+            g = self.grad[off:off + n].view_as(p)
             p.grad = g
             views[id(p)] = g
-            adam[i] = _lib.dfwfm_adam_tensor(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n)
+            if optimizer == "adam":
+                m, v = (t[off:off + n].view_as(p) for t in (self.exp_avg, self.exp_avg_sq))
+                adam[i] = _lib.dfwfm_adam_tensor(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n)
+            else:
+                st = None if self.opt_state is None else self.opt_state[off:off + n].data_ptr()
+                adam[i] = _lib.dfwfm_optim_tensor(p.data_ptr(), g.data_ptr(), st, n)
         self.params, self.adam, self.n_adam = params, adam, len(params)
+        self.offs = offs
         self.n_main = sum(1 for p in params if id(p) not in mlp_ids)  # params are ordered with the MLP last
-        self.adam_mlp = ctypes.cast(ctypes.addressof(adam) + self.n_main * ctypes.sizeof(_lib.dfwfm_adam_tensor),
-                                    ctypes.POINTER(_lib.dfwfm_adam_tensor))
+        self.adam_mlp = ctypes.cast(ctypes.addressof(adam) + self.n_main * ctypes.sizeof(tensor_t),
+                                    ctypes.POINTER(tensor_t))
         self.n_cat = sum(1 for p in params if id(p) in cat_ids)  # params are ordered with the tables first
-        self.adam_rest = ctypes.cast(ctypes.addressof(adam) + self.n_cat * ctypes.sizeof(_lib.dfwfm_adam_tensor),
-                                     ctypes.POINTER(_lib.dfwfm_adam_tensor))
+        self.adam_rest = ctypes.cast(ctypes.addressof(adam) + self.n_cat * ctypes.sizeof(tensor_t),
+                                     ctypes.POINTER(tensor_t))
+        if optimizer != "adam":
+            self.hyper = _lib.dfwfm_optim_hyper(_lib.OPTIM_KINDS[optimizer][0], 0, self.lr, self.wd, self.momentum,
+                                                self.alpha, self.eps)
         # one process: Adam as two launches, the categorical tables (state_t) and the rest (state), on every path
         # (eager, graph, step_many), so the two counters always hold the same step
         self.split_adam = dist is None and 0 < self.n_cat < len(params)
@@ -519,7 +555,19 @@ class FusedTrainStep:
 
     def _adam_range(self, tensors, n, state):
         """The dense Adam of n tensors on one state block: the rate a kernel argument, or with lr_schedule read from
-        the trainer's schedule block when the kernels run."""
+        the trainer's schedule block when the kernels run.  With another optimizer (include/dfwfm_optim.h) the list is
+        that optimizer's and so is the call; the state block, the counter's advance and the schedule are the same."""
+        if self.optimizer != "adam":
+            if self.sched is not None:
+                _lib.check(self.L.dfwfm_optim_step_dev_sched(tensors, n, ctypes.byref(self.hyper),
+                                                             ctypes.c_void_p(self.sched.data_ptr()),
+                                                             ctypes.c_void_p(state.data_ptr()), self._stream()),
+                           "dfwfm_optim_step_dev_sched")
+                return
+            _lib.check(self.L.dfwfm_optim_step_dev(tensors, n, ctypes.byref(self.hyper),
+                                                   ctypes.c_void_p(state.data_ptr()), self._stream()),
+                       "dfwfm_optim_step_dev")
+            return
         b1, b2 = self.betas
         if self.sched is not None:
             _lib.check(self.L.dfwfm_adam_step_dev_sched(tensors, n, ctypes.c_void_p(self.sched.data_ptr()), b1, b2,
@@ -1057,6 +1105,16 @@ def fit(model, Xi_train, Xv_train, y_train, Xi_valid=None, Xv_valid=None, y_vali
     # other optimizers / the KD loss go through autograd + the optimizer
     fused = model.optimizer_type == "adam" and not teacher_model and getattr(model, "fused_fit", True) and \
         device.type == "cuda"  # on the CPU: the host kernels through autograd + torch.optim.Adam
+    # fused_optimizer: SGD / Adagrad / RMSprop on the fused step too (include/dfwfm_optim.h), opt-in
+    fused_opt = bool(getattr(model, "fused_optimizer", False))
+    optimizer = "adam"
+    if fused_opt and model.optimizer_type != "adam":
+        optimizer = model.optimizer_type if model.optimizer_type in ("rmsp", "adag") else "sgd"
+        fused = not teacher_model and getattr(model, "fused_fit", True) and device.type == "cuda"
+    if fused_opt and not fused:
+        # never train silently through another path: the switch asks for the fused step
+        raise ValueError("fused_optimizer needs the fused training step: a module on a HIP device, "
+                         "no teacher model and fused_fit on")
     bs = model.batch_size
     gbs = bs * world
     lazy = bool(getattr(model, "lazy_table_adam", False))
@@ -1070,7 +1128,9 @@ def fit(model, Xi_train, Xv_train, y_train, Xi_valid=None, Xv_valid=None, y_vali
         raise ValueError("lr_schedule needs the fused training step: a module on a HIP device, "
                          "optimizer_type='adam', no teacher model and fused_fit on")
     trainer = FusedTrainStep(model, bs, lr=model.learning_rate, weight_decay=model.weight_decay,
-                             dist=dist, lazy_table_adam=lazy, lr_schedule=sched) if fused else None
+                             dist=dist, lazy_table_adam=lazy, lr_schedule=sched,
+                             **({} if optimizer == "adam" else dict(optimizer=optimizer, momentum=model.momentum))) \
+        if fused else None
     try:
         return _fit_loop(model, trainer, dist, rank, world, Xi_train, Xv_train, y_train, x_size, ncat, is_valid,
                          Xi_valid if is_valid else None, Xv_valid if is_valid else None,
