@@ -2,7 +2,7 @@
 
     python tools/bench_train.py [--gpus N] [--steps K] [--warmup W] [--batch 4096] [--first-order lw|fwlw]
                                 [--lr-schedule 1:1e-4,2000:1e-3,200000:1e-4]
-                                [--optimizer adam|sgd|adag|rmsp] [--momentum M]
+                                [--optimizer adam|sgd|adag|rmsp] [--momentum M] [--lazy-tables]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 tools/bench_train.py
 
 One step = the reference's fit() inner loop body (model/DeepFMs.py:619-637) on a resident synthetic
@@ -53,6 +53,10 @@ def main():
     ap.add_argument("--lazy-adam", action="store_true",
                     help="fused, one rank: the categorical tables' Adam over the rows each batch touched only "
                          "(FusedTrainStep(lazy_table_adam=True); not the reference's dense semantics)")
+    ap.add_argument("--lazy-tables", action="store_true",
+                    help="fused, one rank: the categorical tables' update over the rows each batch touched only, "
+                         "whichever --optimizer runs (FusedTrainStep(lazy_tables=True), include/dfwfm_lazy_optim.h; "
+                         "with adam the same as --lazy-adam); composes with --momentum, --atomic and --lr-schedule")
     ap.add_argument("--lr-schedule", default=None, metavar="STEP:LR[,STEP:LR...]",
                     help="fused: the learning rate from a piecewise-linear schedule evaluated on the device every step "
                          "(FusedTrainStep(lr_schedule=...), e.g. \"1:1e-4,2000:1e-3,200000:1e-4\") instead of the "
@@ -126,6 +130,7 @@ def main():
         # device input buffers; --copy-inputs copies each batch into the step's own buffers first
         trainer = FusedTrainStep(model, B, lr=1e-3, weight_decay=3e-7, dist=dist, resident_inputs=not a.copy_inputs,
                                  deterministic=not a.atomic, lazy_table_adam=a.lazy_adam, lr_schedule=schedule,
+                                 **(dict(lazy_tables=True) if a.lazy_tables else {}),
                                  **({} if a.optimizer == "adam" else dict(optimizer=a.optimizer, momentum=a.momentum)))
 
     def step(i):
@@ -176,11 +181,12 @@ def main():
            "first_order": a.first_order, "dropout": not a.no_dropout, "wall_s": round(wall, 3),
            "host_enqueue_us_per_step": round(host * 1e6 / a.steps, 1),
            "mode": a.mode, "deterministic": not a.atomic, "steps_per_graph": K, "inputs": "copied" if (a.copy_inputs or a.mode != "fused") else "resident (read in place)",
-           "lazy_adam": bool(trainer is not None and getattr(trainer, "lazy", False)),
+           "lazy_adam": bool(trainer is not None and getattr(trainer, "lazy", False) and a.optimizer == "adam"),
+           "lazy_tables": bool(trainer is not None and getattr(trainer, "lazy", False)),
            "lr_schedule": schedule, "optimizer": a.optimizer, "momentum": a.momentum,
            "optimizer_bytes_per_param": opt_bytes,
            "final_loss_sum": round(float(loss.item()), 4)}
-    if res["lazy_adam"]:
+    if res["lazy_tables"]:
         # distinct rows the four resident batches touch per step, per table family (what the lazy step updates)
         res["touched_rows_per_step"] = touched_rows(model, [b[0] for b in batches])
     if trainer is not None and getattr(trainer, "sparse", False):

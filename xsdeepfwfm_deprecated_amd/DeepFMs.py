@@ -171,7 +171,14 @@ class DeepFMs(nn.Module):
         # those optimizers stay on the autograd path.  fit() raises ValueError when it is set and the fused step is
         # not the path (a CPU module, a teacher model, fused_fit off), as for lazy_table_adam
         self.fused_optimizer = False
-        self._defer_index_check = 0     # >0 inside a batched caller: one flag read at its end, not per batch
+        # fit()'s fused step updates only the rows of the categorical tables that each batch touched, whichever
+        # optimizer it runs (FusedTrainStep(lazy_tables=True)): with Adam this is lazy_table_adam; with optimizer_type
+        # 'sgd' / 'adag' / 'rmsp' (and fused_optimizer on) include/dfwfm_lazy_optim.h -- the dense step's exact bits
+        # for plain SGD and Adagrad without weight decay, NOT the dense optimizer for momentum-SGD, RMSprop or any
+        # weight decay.  Off by default; fit() raises ValueError when it is set and the fused step is not the path (a
+        # CPU module, a teacher model, fused_fit off, a non-Adam optimizer_type without fused_optimizer)
+        self.lazy_tables = False
+        self._defer_index_check = 0    # >0 inside a batched caller: one flag read at its end, not per batch
         self._engine = None
 
         np.random.seed(self.random_seed)

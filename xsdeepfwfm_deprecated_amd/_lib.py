@@ -25,7 +25,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libdfwfm.so")
 LOAD_PATH = os.path.join(PKG_DIR, os.environ["DFWFM_LIB"]) if os.environ.get("DFWFM_LIB") else LIB_PATH
 SOURCES = ["dfwfm_kernels.hip", "dfwfm_fwd32.hip", "dfwfm_ftrain.hip", "dfwfm_train.hip", "dfwfm_prune.hip", "dfwfm_metrics.hip", "dfwfm_sparse.hip",
            "dfwfm_spmlp.hip", "dfwfm_serve.hip", "dfwfm_bf16.hip", "dfwfm_bf16_fused.hip", "dfwfm_int8.hip", "dfwfm_lazy_adam.hip",
-           "dfwfm_optim.hip",
+           "dfwfm_optim.hip", "dfwfm_lazy_optim.hip",
            "dfwfm_capi.hip"]
 # the forward / backward kernel templates are instantiated once per embedding size, each size in its own
 # translation unit (-DDFWFM_KD=<D>) so they compile in parallel; the plain object holds everything else
@@ -40,6 +40,7 @@ def _units():
         u += [(s, f"{os.path.splitext(s)[0]}_d{d}.o", [f"-DDFWFM_KD={d}"]) for d in EMB_SIZES]
     return u
 HEADERS = ["dfwfm_internal.h", "dfwfm_device.h", "dfwfm_fused_stage.h", "dfwfm_adam.h", "dfwfm_optim.h",
+           "dfwfm_lazy_optim.h",
            os.path.join("..", "..", "include", "dfwfm.h"),
            os.path.join("..", "..", "include", "dfwfm_serve.h"), os.path.join("..", "..", "include", "dfwfm_bf16.h"),
            os.path.join("..", "..", "include", "dfwfm_bf16_fused.h"), os.path.join("..", "..", "include", "dfwfm_fold.h"),
@@ -48,7 +49,8 @@ HEADERS = ["dfwfm_internal.h", "dfwfm_device.h", "dfwfm_fused_stage.h", "dfwfm_a
            os.path.join("..", "..", "include", "dfwfm_half_tables.h"),
            os.path.join("..", "..", "include", "dfwfm_int8_tables.h"),
            os.path.join("..", "..", "include", "dfwfm_lr_schedule.h"),
-           os.path.join("..", "..", "include", "dfwfm_optim.h")]
+           os.path.join("..", "..", "include", "dfwfm_optim.h"),
+           os.path.join("..", "..", "include", "dfwfm_lazy_optim.h")]
 ARCH = os.environ.get("DFWFM_OFFLOAD_ARCH", "gfx950")
 CPU_PATH = os.path.join(PKG_DIR, "libdfwfm_cpu.so")
 CPU_SOURCES = ["dfwfm_cpu.cpp"]
@@ -126,6 +128,13 @@ class dfwfm_optim_hyper(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int32), ("reserved", ctypes.c_int32), ("lr", ctypes.c_double),
                 ("weight_decay", ctypes.c_double), ("momentum", ctypes.c_double), ("alpha", ctypes.c_double),
                 ("eps", ctypes.c_double)]
+
+
+class dfwfm_lazy_optim_table(ctypes.Structure):
+    _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("state", ctypes.c_void_p),
+                ("stamp", ctypes.c_void_p), ("rows", ctypes.c_int64), ("key_range", ctypes.c_int64),
+                ("c", ctypes.c_int64), ("width", ctypes.c_int32), ("column", ctypes.c_int32),
+                ("kind", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 class dfwfm_sparse_dest(ctypes.Structure):
@@ -295,6 +304,17 @@ OPTIM_SIGNATURES = {
     "dfwfm_optim_elem_ref": (ctypes.c_int, [ctypes.POINTER(dfwfm_optim_hyper), ctypes.c_int64,
                                             ctypes.POINTER(ctypes.c_float), ctypes.c_float,
                                             ctypes.POINTER(ctypes.c_float)]),
+}
+# the row-lazy SGD, Adagrad and RMSprop steps of the categorical tables (include/dfwfm_lazy_optim.h): same library, its
+# own header and ABI version
+LAZY_OPTIM_SIGNATURES = {
+    "dfwfm_lazy_optim_abi_version": (ctypes.c_int, []),
+    "dfwfm_lazy_optim_step_dev": (ctypes.c_int, [ctypes.POINTER(dfwfm_lazy_optim_table), ctypes.c_int32, _P,
+                                                 ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(dfwfm_optim_hyper),
+                                                 _P, _P]),
+    "dfwfm_lazy_optim_step_dev_sched": (ctypes.c_int, [ctypes.POINTER(dfwfm_lazy_optim_table), ctypes.c_int32, _P,
+                                                       ctypes.c_int64, ctypes.c_int64,
+                                                       ctypes.POINTER(dfwfm_optim_hyper), _P, _P, _P]),
 }
 # FusedTrainStep's optimizer names (the reference's optimizer_type values) -> (kind, default eps, needs a state array
 # whatever the momentum)
@@ -578,6 +598,12 @@ def lib():
             fn.argtypes = args
         if L.dfwfm_optim_abi_version() != 1:
             raise DfwfmError("libdfwfm optim ABI mismatch")
+        for name, (res, args) in LAZY_OPTIM_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        if L.dfwfm_lazy_optim_abi_version() != 1:
+            raise DfwfmError("libdfwfm lazy optim ABI mismatch")
         _lib = L
     return _lib
 

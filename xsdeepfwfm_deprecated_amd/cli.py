@@ -115,6 +115,11 @@ def get_parser():
       help="training on a HIP device: optimizer_type 'sgd', 'adag' and 'rmsp' run on the graph-replayed fused step too "
            "(DeepFMs.fused_optimizer, include/dfwfm_optim.h) instead of autograd + torch.optim; fit() raises when the "
            "fused step is not the path")
+    a("-lazy_tables", default=0, type=int, choices=[0, 1],
+      help="training on a HIP device on the fused step: the categorical tables' update touches only the rows each "
+           "batch touched, whichever optimizer runs (DeepFMs.lazy_tables, include/dfwfm_lazy_optim.h; with Adam the "
+           "same as -lazy_adam).  Plain SGD and Adagrad without -l2 give the dense step's exact bits; momentum-SGD, "
+           "RMSprop and any -l2 are NOT the dense optimizer: untouched rows get no decay and no L2")
     return p
 
 
@@ -169,4 +174,5 @@ def get_model(cuda, feature_sizes, pars, dynamic_quantization=False, static_quan
     m.lazy_table_adam = bool(getattr(pars, "lazy_adam", 0))  # fit() raises if the fused Adam step is not the path
     m.lr_schedule = getattr(pars, "lr_schedule", None)  # fit() raises if the fused Adam step is not the path
     m.fused_optimizer = bool(getattr(pars, "fused_optimizer", 0))  # fit() raises if the fused step is not the path
+    m.lazy_tables = bool(getattr(pars, "lazy_tables", 0))  # fit() raises if the fused step is not the path
     return m

@@ -23,7 +23,9 @@
 #include "../../include/dfwfm_half_tables.h"
 #include "../../include/dfwfm_int8_tables.h"
 #include "../../include/dfwfm_optim.h"
+#include "../../include/dfwfm_lazy_optim.h"
 #include "dfwfm_optim.h"
+#include "dfwfm_lazy_optim.h"
 
 using namespace dfwfm;
 
@@ -2489,6 +2491,98 @@ int dfwfm_optim_elem_ref(const dfwfm_optim_hyper* hyper, int64_t step, float* p,
     default: optim_elem<kOptRmsprop>(c, *p, g, *state); break;
   }
   return DFWFM_OK;
+}
+
+// ---------------------------------------------------------------- include/dfwfm_lazy_optim.h
+int dfwfm_lazy_optim_abi_version(void) { return DFWFM_LAZY_OPTIM_ABI_VERSION; }
+
+// dfwfm_lazy_optim_step_dev and, with a schedule block (sched != null: hyper->lr unused),
+// dfwfm_lazy_optim_step_dev_sched
+static int lazy_optim_step_dev_impl(const dfwfm_lazy_optim_table* t, int32_t n, const int64_t* xi, int64_t xi_stride,
+                                    int64_t batch, const dfwfm_optim_hyper* hyper, const LrSchedule* sched,
+                                    void* state_dev, void* stream) {
+  int kind = 0;
+  if (int rc = optim_hyper_check(hyper, sched == nullptr, &kind)) return rc;
+  if (!state_dev) return fail(DFWFM_ERR_INVALID_ARG, "null state block");
+  if (n < 0) return fail(DFWFM_ERR_INVALID_ARG, "negative table count");
+  if (batch < 0) return fail(DFWFM_ERR_INVALID_ARG, "negative batch");
+  if (n > 0 && !t) return fail(DFWFM_ERR_INVALID_ARG, "null table array");
+  if (batch > 0 && n > 0 && (!xi || xi_stride < 1)) return fail(DFWFM_ERR_INVALID_ARG, "null xi or xi_stride < 1");
+  for (int i = 0; i < n; ++i) {
+    const dfwfm_lazy_optim_table& x = t[i];
+    if (!x.param || !x.grad || !x.stamp) return fail(DFWFM_ERR_INVALID_ARG, "lazy table %d: null pointer", i);
+    if (kind != kOptSgd && !x.state) return fail(DFWFM_ERR_INVALID_ARG, "lazy table %d: null state pointer", i);
+    if (x.rows < 1 || x.width < 1 || x.key_range < 1)
+      return fail(DFWFM_ERR_INVALID_ARG, "lazy table %d: rows, width and key_range must be >= 1", i);
+    if (x.column < 0 || (batch > 0 && x.column >= xi_stride))
+      return fail(DFWFM_ERR_INVALID_ARG, "lazy table %d: column %d outside xi's %lld", i, x.column, (long long)xi_stride);
+    if (x.kind != DFWFM_LAZY_PLAIN && x.kind != DFWFM_LAZY_QUOTIENT && x.kind != DFWFM_LAZY_REMAINDER)
+      return fail(DFWFM_ERR_INVALID_ARG, "lazy table %d: kind %d", i, x.kind);
+    if (x.kind != DFWFM_LAZY_PLAIN && x.c < 1) return fail(DFWFM_ERR_INVALID_ARG, "lazy table %d: c < 1 on a QR kind", i);
+    // every key of [0, key_range) must land on a row of the table: the kernel indexes without a row count
+    const int64_t top = x.kind == DFWFM_LAZY_PLAIN ? x.key_range - 1
+                        : x.kind == DFWFM_LAZY_QUOTIENT ? (x.key_range - 1) / x.c
+                                                        : (x.c < x.key_range ? x.c : x.key_range) - 1;
+    if (top >= x.rows)
+      return fail(DFWFM_ERR_INVALID_ARG, "lazy table %d: key range %lld reaches row %lld of %lld", i,
+                  (long long)x.key_range, (long long)top, (long long)x.rows);
+    if (lazy_blocks(x.width, batch) > 0x3fffffff) return fail(DFWFM_ERR_UNSUPPORTED, "lazy table %d: batch too large", i);
+  }
+  LazyOptimArgs a;
+  memset(&a, 0, sizeof a);
+  a.xi = xi;
+  a.xi_stride = xi_stride;
+  a.batch = batch;
+  a.st = reinterpret_cast<AdamDevState*>(state_dev);
+  a.sched = sched;
+  a.h = OptimHyper{hyper->lr, hyper->weight_decay, hyper->momentum, hyper->alpha, hyper->eps};
+  // the tables' launches (<= kLazyOptimList tables each); the last one advances the device step counter (without a
+  // table or a sample it is one empty workgroup)
+  LazyOptimList list;
+  memset(&list, 0, sizeof list);
+  const int nt = batch > 0 ? n : 0;
+  int64_t blocks = 0;
+  for (int i = 0; i <= nt; ++i) {
+    const bool last = i == nt;
+    const int64_t nb = last ? 0 : lazy_blocks(t[i].width, batch);
+    if (last || list.n == kLazyOptimList || blocks + nb > 0x7fffffff) {
+      a.bump = last ? 1 : 0;
+      a.nblocks = (int32_t)blocks;
+      hipError_t e = launch_lazy_optim(kind, list, a, (hipStream_t)stream);
+      if (e != hipSuccess) return hip_fail(e, "lazy optim launch");
+      list.n = 0;
+      blocks = 0;
+    }
+    if (last) break;
+    const dfwfm_lazy_optim_table& x = t[i];
+    LazyOptimTable& d = list.t[list.n];
+    d.p = x.param;
+    d.g = x.grad;
+    d.s = kind == kOptSgd ? nullptr : x.state;
+    d.stamp = x.stamp;
+    d.key_range = x.key_range;
+    d.c = x.c;
+    d.width = x.width;
+    d.column = x.column;
+    d.kind = x.kind;
+    d.block0 = (int32_t)blocks;
+    ++list.n;
+    blocks += nb;
+  }
+  return DFWFM_OK;
+}
+
+int dfwfm_lazy_optim_step_dev(const dfwfm_lazy_optim_table* t, int32_t n, const int64_t* xi, int64_t xi_stride,
+                              int64_t batch, const dfwfm_optim_hyper* hyper, void* state_dev, void* stream) {
+  return lazy_optim_step_dev_impl(t, n, xi, xi_stride, batch, hyper, nullptr, state_dev, stream);
+}
+
+int dfwfm_lazy_optim_step_dev_sched(const dfwfm_lazy_optim_table* t, int32_t n, const int64_t* xi, int64_t xi_stride,
+                                    int64_t batch, const dfwfm_optim_hyper* hyper, const void* sched_dev,
+                                    void* state_dev, void* stream) {
+  if (!sched_dev) return fail(DFWFM_ERR_INVALID_ARG, "null schedule block");
+  return lazy_optim_step_dev_impl(t, n, xi, xi_stride, batch, hyper, reinterpret_cast<const LrSchedule*>(sched_dev),
+                                  state_dev, stream);
 }
 
 int dfwfm_bce_grad(const float* z, const float* y, int64_t n, double denom, float* dz, float* loss_sum,

@@ -60,6 +60,21 @@ __host__ __device__ __forceinline__ void optim_elem(const OptimCoef& c, float& p
   p = p + num / den;                                                      // param.addcdiv_(grad, den, value=-lr)
 }
 
+// the last workgroup of a step's last launch (ticket == nwg - 1): advance the counter.  The block's f32 slots hold
+// the last step's scalars for diagnostics, as after an Adam step: the rate's slot gets lr, the others what applies.
+// (Shared by the dense kernels, dfwfm_optim.hip, and the row-lazy one, dfwfm_lazy_optim.hip.)
+__device__ __forceinline__ void optim_advance(AdamDevState* __restrict__ st, const OptimCoef& c, int64_t step) {
+  st->step_size = -c.neg_lr;
+  st->omb1 = c.mom;
+  st->b2 = c.alpha;
+  st->omb2 = c.oma;
+  st->eps = c.eps;
+  st->wd = c.wd;
+  st->bc2_sqrt = 0.f;
+  st->ticket = 0;
+  st->step = step;
+}
+
 // One tensor of a launch: 32 bytes, so that more tensors than Adam's 91 fit a launch's arguments.
 struct OptimTensor {
   float* p;

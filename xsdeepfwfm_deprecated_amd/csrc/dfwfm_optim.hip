@@ -74,20 +74,6 @@ __device__ __forceinline__ void optim_block(const OptimList& list, const OptimCo
   }
 }
 
-// the last workgroup of a step's last launch (ticket == nwg - 1): advance the counter.  The block's f32 slots hold
-// the last step's scalars for diagnostics, as after an Adam step: the rate's slot gets lr, the others what applies.
-__device__ __forceinline__ void optim_advance(AdamDevState* __restrict__ st, const OptimCoef& c, int64_t step) {
-  st->step_size = -c.neg_lr;
-  st->omb1 = c.mom;
-  st->b2 = c.alpha;
-  st->omb2 = c.oma;
-  st->eps = c.eps;
-  st->wd = c.wd;
-  st->bc2_sqrt = 0.f;
-  st->ticket = 0;
-  st->step = step;
-}
-
 // SCHED: the first wave evaluates the schedule at the step (lr_schedule_value, dfwfm_adam.h) and its lane 0 forms the
 // scalars with that double in the place of a.h.lr; nothing else differs.
 template <int K, bool SCHED>

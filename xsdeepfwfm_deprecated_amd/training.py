@@ -202,15 +202,27 @@ class FusedTrainStep:
     step_many, resident inputs, data parallelism, lr_schedule.  The state is ONE flat buffer (``opt_state``: momentum
     buffer, sum or square_avg, laid out like the gradient buffer) and none at all for SGD with momentum == 0;
     ``exp_avg`` / ``exp_avg_sq`` are then None.  ``eps`` None: the kind's default (Adam and RMSprop 1e-8, Adagrad
-    1e-10).  lazy_table_adam is Adam's: with another optimizer it raises ValueError."""
+    1e-10).  lazy_table_adam is Adam's: with another optimizer it raises ValueError.
+
+    lazy_tables: the categorical tables' update touches only the rows the step's batch touched, whichever optimizer
+    the step runs.  With "adam" it IS lazy_table_adam (same calls, same bits).  With "sgd", "adag" or "rmsp" the
+    tables go through include/dfwfm_lazy_optim.h: the dense kernels' own per-element arithmetic at the global step on
+    the touched rows, whose gradient rows it zeroes, so the tables' region of the gradient buffer is not filled either.
+    Plain SGD and Adagrad with weight_decay == 0 give the dense step's exact bits; momentum-SGD, RMSprop and any
+    weight_decay != 0 are NOT the dense optimizer (an untouched row's buffer or square_avg does not decay, a
+    momentum-SGD row is not moved by its buffer, an untouched row gets no L2).  Everything that is not a categorical
+    table stays on the dense update.  One process only."""
 
     def __init__(self, model, batch_size, lr=1e-3, weight_decay=0.0, betas=(0.9, 0.999), eps=None,
                  use_graph=True, dist=None, sparse_exchange=True, resident_inputs=False, max_graph_sets=8,
                  max_many_sets=2, deterministic=None, lazy_table_adam=False, lr_schedule=None,
-                 optimizer="adam", momentum=0.0, alpha=0.99):
+                 optimizer="adam", momentum=0.0, alpha=0.99, lazy_tables=False):
         dev = model._device()
         if dev.type != "cuda":
             raise _lib.DfwfmError("FusedTrainStep runs only on a HIP device")
+        if lazy_tables and dist is not None:
+            raise NotImplementedError("lazy_tables under data parallelism: the touched rows are the union of the "
+                                      "ranks' exchanged lists, which the lazy step does not read yet")
         if lazy_table_adam and dist is not None:
             # the touched set of a data-parallel step is the union of every rank's exchanged lists (DESIGN.md section 9)
             raise NotImplementedError("lazy_table_adam under data parallelism: the touched rows are the union of the "
@@ -318,11 +330,13 @@ class FusedTrainStep:
         # one process: Adam as two launches, the categorical tables (state_t) and the rest (state), on every path
         # (eager, graph, step_many), so the two counters always hold the same step
         self.split_adam = dist is None and 0 < self.n_cat < len(params)
-        # lazy_table_adam: the tables' Adam over the batch's touched rows only (no categorical table: nothing to do)
-        self.lazy = bool(lazy_table_adam) and self.n_cat > 0
+        # lazy_table_adam / lazy_tables: the tables' update over the batch's touched rows only (no categorical table:
+        # nothing to do)
+        self.lazy = bool(lazy_table_adam or lazy_tables) and self.n_cat > 0
         if self.lazy:
             if not self.split_adam:
-                raise NotImplementedError("lazy_table_adam: a model whose only trainable parameters are tables")
+                raise NotImplementedError(("lazy_table_adam" if lazy_table_adam else "lazy_tables") +
+                                          ": a model whose only trainable parameters are tables")
             self._setup_lazy(fields, params[:self.n_cat], views)
         ptr = lambda t: None if t is None else views[id(t)].data_ptr()  # noqa: E731
         # sparse exchange: the backward scatters the categorical tables' gradients into a rank-local buffer (same
@@ -426,7 +440,8 @@ class FusedTrainStep:
                            "dfwfm_sparse_grads_apply")
 
     def _setup_lazy(self, fields, tables, views):
-        """The table descriptors of dfwfm_lazy_adam_step_dev: every categorical table with its xi column, its key
+        """The table descriptors of dfwfm_lazy_adam_step_dev, or with another optimizer of dfwfm_lazy_optim_step_dev
+        (one state array, over opt_state; none for plain SGD): every categorical table with its xi column, its key
         range (the forward's: a QR field accepts every key whose quotient row exists) and its slice of the stamps."""
         desc = {}
         for f in range(self.model.num, self.model.field_size):
@@ -442,26 +457,46 @@ class FusedTrainStep:
                 if r is not None:
                     desc[id(r)] = (f - self.model.num, keys, _lib.LAZY_REMAINDER, c)
         self.lazy_stamp = torch.zeros(sum(int(p.shape[0]) for p in tables), dtype=torch.int32, device=self.dev)
-        self.lazy_tables = (_lib.dfwfm_lazy_adam_table * len(tables))()
+        adam = self.optimizer == "adam"
+        self.lazy_tables = ((_lib.dfwfm_lazy_adam_table if adam else _lib.dfwfm_lazy_optim_table) * len(tables))()
         row0 = 0
         for i, p in enumerate(tables):
             col, keys, kind, c = desc[id(p)]
             rows, width = int(p.shape[0]), p.numel() // int(p.shape[0])
             g = views[id(p)]
             off = (g.data_ptr() - self.grad.data_ptr()) // 4
-            self.lazy_tables[i] = _lib.dfwfm_lazy_adam_table(
-                p.data_ptr(), g.data_ptr(), self.exp_avg[off:].data_ptr(), self.exp_avg_sq[off:].data_ptr(),
-                self.lazy_stamp[row0:].data_ptr(), rows, keys, c, width, col, kind, 0)
+            if adam:
+                self.lazy_tables[i] = _lib.dfwfm_lazy_adam_table(
+                    p.data_ptr(), g.data_ptr(), self.exp_avg[off:].data_ptr(), self.exp_avg_sq[off:].data_ptr(),
+                    self.lazy_stamp[row0:].data_ptr(), rows, keys, c, width, col, kind, 0)
+            else:
+                st = None if self.opt_state is None else self.opt_state[off:].data_ptr()
+                self.lazy_tables[i] = _lib.dfwfm_lazy_optim_table(
+                    p.data_ptr(), g.data_ptr(), st, self.lazy_stamp[row0:].data_ptr(), rows, keys, c, width, col,
+                    kind, 0)
             row0 += rows
 
     def _adam_tables(self, n):
-        """The categorical tables' Adam on state_t: every row (dense), or under lazy_table_adam the rows that the
-        first n samples of the step's input buffer touch."""
+        """The categorical tables' update on state_t: every row (dense), or under lazy_table_adam / lazy_tables the
+        rows that the first n samples of the step's input buffer touch (Adam: include/dfwfm_lazy_adam.h; another
+        optimizer: include/dfwfm_lazy_optim.h)."""
         if not self.lazy:
             self._adam_range(self.adam, self.n_cat, self.state_t)
             return
-        b1, b2 = self.betas
         xi = self._in[0]
+        if self.optimizer != "adam":
+            if self.sched is not None:
+                _lib.check(self.L.dfwfm_lazy_optim_step_dev_sched(
+                    self.lazy_tables, self.n_cat, ctypes.c_void_p(xi.data_ptr()), xi.stride(0), n,
+                    ctypes.byref(self.hyper), ctypes.c_void_p(self.sched.data_ptr()),
+                    ctypes.c_void_p(self.state_t.data_ptr()), self._stream()), "dfwfm_lazy_optim_step_dev_sched")
+                return
+            _lib.check(self.L.dfwfm_lazy_optim_step_dev(
+                self.lazy_tables, self.n_cat, ctypes.c_void_p(xi.data_ptr()), xi.stride(0), n,
+                ctypes.byref(self.hyper), ctypes.c_void_p(self.state_t.data_ptr()), self._stream()),
+                "dfwfm_lazy_optim_step_dev")
+            return
+        b1, b2 = self.betas
         if self.sched is not None:
             _lib.check(self.L.dfwfm_lazy_adam_step_dev_sched(
                 self.lazy_tables, self.n_cat, ctypes.c_void_p(xi.data_ptr()), xi.stride(0), n,
@@ -501,8 +536,8 @@ class FusedTrainStep:
     def _part1(self, n, denom, phases=None):
         L, st, h = self.L, self._stream(), self.eng.handle
         self.eng.set_deterministic(self.deterministic)  # read when the backward launches are enqueued / captured
-        # the dense weights re-packed and the gradient buffer zeroed in one launch (lazy_table_adam: all but the
-        # categorical tables' region, which the lazy step leaves zero)
+        # the dense weights re-packed and the gradient buffer zeroed in one launch (lazy_table_adam / lazy_tables: all
+        # but the categorical tables' region, which the lazy step leaves zero)
         z0 = self.n_tables if self.lazy else 0
         _lib.check(L.dfwfm_model_set_dense_zero(h, *self.dense_args, ctypes.c_void_p(self.grad[z0:].data_ptr()),
                                                 self.grad.numel() - z0, st), "dfwfm_model_set_dense_zero")
@@ -1122,13 +1157,18 @@ def fit(model, Xi_train, Xv_train, y_train, Xi_valid=None, Xv_valid=None, y_vali
         # never train silently with another optimizer's semantics: the lazy update exists on the fused step only
         raise ValueError("lazy_table_adam needs the fused training step: a module on a HIP device, "
                          "optimizer_type='adam', no teacher model and fused_fit on")
+    lazy_tabs = bool(getattr(model, "lazy_tables", False))
+    if lazy_tabs and not fused:
+        # never train silently through the dense update: the row-lazy steps exist on the fused step only
+        raise ValueError("lazy_tables needs the fused training step: a module on a HIP device, no teacher model, "
+                         "fused_fit on, and optimizer_type='adam' or fused_optimizer on")
     sched = getattr(model, "lr_schedule", None)
     if sched is not None and not fused:
         # never train silently at another rate: the schedule exists on the fused step only
         raise ValueError("lr_schedule needs the fused training step: a module on a HIP device, "
                          "optimizer_type='adam', no teacher model and fused_fit on")
     trainer = FusedTrainStep(model, bs, lr=model.learning_rate, weight_decay=model.weight_decay,
-                             dist=dist, lazy_table_adam=lazy, lr_schedule=sched,
+                             dist=dist, lazy_table_adam=lazy, lr_schedule=sched, lazy_tables=lazy_tabs,
                              **({} if optimizer == "adam" else dict(optimizer=optimizer, momentum=model.momentum))) \
         if fused else None
     try:
