@@ -3,6 +3,7 @@
     python tools/bench_train.py [--gpus N] [--steps K] [--warmup W] [--batch 4096] [--first-order lw|fwlw]
                                 [--lr-schedule 1:1e-4,2000:1e-3,200000:1e-4]
                                 [--optimizer adam|sgd|adag|rmsp] [--momentum M] [--lazy-tables]
+                                [--exchange-world1 [--lazy-adam|--lazy-tables] --lazy-exchange [--apply-worlds 1,2,4,8]]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 tools/bench_train.py
 
 One step = the reference's fit() inner loop body (model/DeepFMs.py:619-637) on a resident synthetic
@@ -57,6 +58,11 @@ def main():
                     help="fused, one rank: the categorical tables' update over the rows each batch touched only, "
                          "whichever --optimizer runs (FusedTrainStep(lazy_tables=True), include/dfwfm_lazy_optim.h; "
                          "with adam the same as --lazy-adam); composes with --momentum, --atomic and --lr-schedule")
+    ap.add_argument("--lazy-exchange", action="store_true",
+                    help="fused, with --exchange-world1 or --gpus N and --lazy-adam / --lazy-tables: the lazy update "
+                         "under data parallelism, over the exchanged touched-row lists "
+                         "(FusedTrainStep(lazy_exchange=True), include/dfwfm_lazy_lists.h); --apply-worlds then times "
+                         "the lists update as well")
     ap.add_argument("--lr-schedule", default=None, metavar="STEP:LR[,STEP:LR...]",
                     help="fused: the learning rate from a piecewise-linear schedule evaluated on the device every step "
                          "(FusedTrainStep(lr_schedule=...), e.g. \"1:1e-4,2000:1e-3,200000:1e-4\") instead of the "
@@ -77,6 +83,9 @@ def main():
             ap.error(str(e))
         if a.mode != "fused":
             ap.error("--lr-schedule needs --mode fused")
+    if a.lazy_exchange and (a.mode != "fused" or not (a.lazy_adam or a.lazy_tables)
+                            or not (a.exchange_world1 or a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1)):
+        ap.error("--lazy-exchange needs --mode fused, --lazy-adam or --lazy-tables, and --exchange-world1 or --gpus N")
     from xsdeepfwfm_deprecated_amd.launch import spawn_ranks
     rc = spawn_ranks(a.gpus)  # before any HIP call
     if rc is not None:
@@ -131,6 +140,7 @@ def main():
         trainer = FusedTrainStep(model, B, lr=1e-3, weight_decay=3e-7, dist=dist, resident_inputs=not a.copy_inputs,
                                  deterministic=not a.atomic, lazy_table_adam=a.lazy_adam, lr_schedule=schedule,
                                  **(dict(lazy_tables=True) if a.lazy_tables else {}),
+                                 **(dict(lazy_exchange=True) if a.lazy_exchange else {}),
                                  **({} if a.optimizer == "adam" else dict(optimizer=a.optimizer, momentum=a.momentum)))
 
     def step(i):
@@ -183,6 +193,7 @@ def main():
            "mode": a.mode, "deterministic": not a.atomic, "steps_per_graph": K, "inputs": "copied" if (a.copy_inputs or a.mode != "fused") else "resident (read in place)",
            "lazy_adam": bool(trainer is not None and getattr(trainer, "lazy", False) and a.optimizer == "adam"),
            "lazy_tables": bool(trainer is not None and getattr(trainer, "lazy", False)),
+           "lazy_exchange": bool(trainer is not None and getattr(trainer, "lazy_lists", False)),
            "lr_schedule": schedule, "optimizer": a.optimizer, "momentum": a.momentum,
            "optimizer_bytes_per_param": opt_bytes,
            "final_loss_sum": round(float(loss.item()), 4)}
@@ -270,7 +281,61 @@ def apply_bench(trainer, model, sizes, B, dev, worlds, reps=50):
         e1.record()
         torch.cuda.synchronize(dev)
         out["world%d_us" % w] = round(e0.elapsed_time(e1) * 1e3 / reps, 2)
+        if getattr(trainer, "lazy_lists", False):
+            out["world%d_lists_us" % w] = lists_bench(trainer, recv, w, grad, dev, reps)
+            # the same rank's lists W times: every row claimed W times (the worst case for claims) but updated once
+            # (the best case for traffic)
+            out["world%d_lists_replicated_us" % w] = lists_bench(trainer, torch.stack([snaps[0]] * w), w, grad, dev,
+                                                                 reps)
     return out
+
+
+def lists_bench(trainer, recv, w, grad, dev, reps):
+    """The list-driven lazy update (include/dfwfm_lazy_lists.h) over W ranks' lists, graph-replayed on copies of the
+    flat buffers with a state block and stamps of its own (the trainer's are not touched): every replay is a fresh
+    step over the same rows.  Microseconds per call."""
+    import ctypes
+    from xsdeepfwfm_deprecated_amd import _lib
+    L = _lib.lib()
+    P = ctypes.c_void_p
+    spans = (_lib.dfwfm_lazy_lists_span * len(trainer.ll_spans))()
+    stamp = torch.zeros_like(trainer.lazy_stamp)
+    keep, row0 = [], 0
+    for i, sp in enumerate(trainer.ll_spans):
+        p = trainer.params[i].detach().clone()
+        keep.append(p)
+        spans[i] = _lib.dfwfm_lazy_lists_span(p.data_ptr(), stamp[row0:].data_ptr(), sp.offset, sp.rows, sp.width, 0)
+        row0 += sp.rows
+    lists = (_lib.dfwfm_lazy_lists_list * (w * len(trainer.sp_fams)))()
+    for r in range(w):
+        rb = recv[r].data_ptr()
+        for k, f in enumerate(trainer.sp_fams):
+            lists[r * len(trainer.sp_fams) + k] = _lib.dfwfm_lazy_lists_list(rb + f["o_dest"], rb + f["o_cnt"],
+                                                                             f["cap"], f["w"], 0)
+    state = torch.zeros_like(trainer.state_t)
+    adam = trainer.optimizer == "adam"
+    bufs = [torch.zeros_like(grad) for _ in range(2 if adam else (0 if trainer.opt_state is None else 1))]
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        st = P(torch.cuda.current_stream(dev).cuda_stream)  # the capture stream
+        if adam:
+            b1, b2 = trainer.betas
+            _lib.check(L.dfwfm_lazy_adam_lists_step_dev(spans, len(spans), lists, len(lists), P(grad.data_ptr()),
+                                                        P(bufs[0].data_ptr()), P(bufs[1].data_ptr()), trainer.lr, b1,
+                                                        b2, trainer.eps, trainer.wd, P(state.data_ptr()), st), "lists")
+        else:
+            _lib.check(L.dfwfm_lazy_optim_lists_step_dev(spans, len(spans), lists, len(lists), P(grad.data_ptr()),
+                                                         P(bufs[0].data_ptr()) if bufs else None,
+                                                         ctypes.byref(trainer.hyper), P(state.data_ptr()), st), "lists")
+    for _ in range(3):
+        g.replay()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        g.replay()
+    e1.record()
+    torch.cuda.synchronize(dev)
+    return round(e0.elapsed_time(e1) * 1e3 / reps, 2)
 
 
 if __name__ == "__main__":

@@ -178,6 +178,11 @@ class DeepFMs(nn.Module):
         # weight decay.  Off by default; fit() raises ValueError when it is set and the fused step is not the path (a
         # CPU module, a teacher model, fused_fit off, a non-Adam optimizer_type without fused_optimizer)
         self.lazy_tables = False
+        # lazy_table_adam / lazy_tables under data parallelism (FusedTrainStep(lazy_exchange=True),
+        # include/dfwfm_lazy_lists.h): "touched" then means touched by the GLOBAL batch, the union of the ranks'
+        # exchanged touched-row lists.  Off by default: fit() under torch.distributed with a lazy switch raises
+        # NotImplementedError without it, and ValueError when it is set without a process group or a lazy switch
+        self.lazy_exchange = False
         self._defer_index_check = 0    # >0 inside a batched caller: one flag read at its end, not per batch
         self._engine = None
 

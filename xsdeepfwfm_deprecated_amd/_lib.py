@@ -25,7 +25,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libdfwfm.so")
 LOAD_PATH = os.path.join(PKG_DIR, os.environ["DFWFM_LIB"]) if os.environ.get("DFWFM_LIB") else LIB_PATH
 SOURCES = ["dfwfm_kernels.hip", "dfwfm_fwd32.hip", "dfwfm_ftrain.hip", "dfwfm_train.hip", "dfwfm_prune.hip", "dfwfm_metrics.hip", "dfwfm_sparse.hip",
            "dfwfm_spmlp.hip", "dfwfm_serve.hip", "dfwfm_bf16.hip", "dfwfm_bf16_fused.hip", "dfwfm_int8.hip", "dfwfm_lazy_adam.hip",
-           "dfwfm_optim.hip", "dfwfm_lazy_optim.hip",
+           "dfwfm_optim.hip", "dfwfm_lazy_optim.hip", "dfwfm_lazy_lists.hip",
            "dfwfm_capi.hip"]
 # the forward / backward kernel templates are instantiated once per embedding size, each size in its own
 # translation unit (-DDFWFM_KD=<D>) so they compile in parallel; the plain object holds everything else
@@ -40,7 +40,7 @@ def _units():
         u += [(s, f"{os.path.splitext(s)[0]}_d{d}.o", [f"-DDFWFM_KD={d}"]) for d in EMB_SIZES]
     return u
 HEADERS = ["dfwfm_internal.h", "dfwfm_device.h", "dfwfm_fused_stage.h", "dfwfm_adam.h", "dfwfm_optim.h",
-           "dfwfm_lazy_optim.h",
+           "dfwfm_lazy_optim.h", "dfwfm_lazy_lists.h",
            os.path.join("..", "..", "include", "dfwfm.h"),
            os.path.join("..", "..", "include", "dfwfm_serve.h"), os.path.join("..", "..", "include", "dfwfm_bf16.h"),
            os.path.join("..", "..", "include", "dfwfm_bf16_fused.h"), os.path.join("..", "..", "include", "dfwfm_fold.h"),
@@ -50,7 +50,8 @@ HEADERS = ["dfwfm_internal.h", "dfwfm_device.h", "dfwfm_fused_stage.h", "dfwfm_a
            os.path.join("..", "..", "include", "dfwfm_int8_tables.h"),
            os.path.join("..", "..", "include", "dfwfm_lr_schedule.h"),
            os.path.join("..", "..", "include", "dfwfm_optim.h"),
-           os.path.join("..", "..", "include", "dfwfm_lazy_optim.h")]
+           os.path.join("..", "..", "include", "dfwfm_lazy_optim.h"),
+           os.path.join("..", "..", "include", "dfwfm_lazy_lists.h")]
 ARCH = os.environ.get("DFWFM_OFFLOAD_ARCH", "gfx950")
 CPU_PATH = os.path.join(PKG_DIR, "libdfwfm_cpu.so")
 CPU_SOURCES = ["dfwfm_cpu.cpp"]
@@ -135,6 +136,16 @@ class dfwfm_lazy_optim_table(ctypes.Structure):
                 ("stamp", ctypes.c_void_p), ("rows", ctypes.c_int64), ("key_range", ctypes.c_int64),
                 ("c", ctypes.c_int64), ("width", ctypes.c_int32), ("column", ctypes.c_int32),
                 ("kind", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class dfwfm_lazy_lists_span(ctypes.Structure):
+    _fields_ = [("param", ctypes.c_void_p), ("stamp", ctypes.c_void_p), ("offset", ctypes.c_int64),
+                ("rows", ctypes.c_int64), ("width", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class dfwfm_lazy_lists_list(ctypes.Structure):
+    _fields_ = [("dest", ctypes.c_void_p), ("count", ctypes.c_void_p), ("cap", ctypes.c_int64),
+                ("width", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 class dfwfm_sparse_dest(ctypes.Structure):
@@ -315,6 +326,20 @@ LAZY_OPTIM_SIGNATURES = {
     "dfwfm_lazy_optim_step_dev_sched": (ctypes.c_int, [ctypes.POINTER(dfwfm_lazy_optim_table), ctypes.c_int32, _P,
                                                        ctypes.c_int64, ctypes.c_int64,
                                                        ctypes.POINTER(dfwfm_optim_hyper), _P, _P, _P]),
+}
+# the row-lazy table optimizers driven by exchanged touched-row lists (include/dfwfm_lazy_lists.h): same library, its
+# own header and ABI version
+_LISTS = [ctypes.POINTER(dfwfm_lazy_lists_span), ctypes.c_int32, ctypes.POINTER(dfwfm_lazy_lists_list), ctypes.c_int32]
+LAZY_LISTS_SIGNATURES = {
+    "dfwfm_lazy_lists_abi_version": (ctypes.c_int, []),
+    "dfwfm_lazy_adam_lists_step_dev": (ctypes.c_int, _LISTS + [_P, _P, _P, ctypes.c_double, ctypes.c_double,
+                                                               ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                                               _P, _P]),
+    "dfwfm_lazy_adam_lists_step_dev_sched": (ctypes.c_int, _LISTS + [_P, _P, _P, _P, ctypes.c_double, ctypes.c_double,
+                                                                     ctypes.c_double, ctypes.c_double, _P, _P]),
+    "dfwfm_lazy_optim_lists_step_dev": (ctypes.c_int, _LISTS + [_P, _P, ctypes.POINTER(dfwfm_optim_hyper), _P, _P]),
+    "dfwfm_lazy_optim_lists_step_dev_sched": (ctypes.c_int, _LISTS + [_P, _P, ctypes.POINTER(dfwfm_optim_hyper), _P,
+                                                                      _P, _P]),
 }
 # FusedTrainStep's optimizer names (the reference's optimizer_type values) -> (kind, default eps, needs a state array
 # whatever the momentum)
@@ -604,6 +629,12 @@ def lib():
             fn.argtypes = args
         if L.dfwfm_lazy_optim_abi_version() != 1:
             raise DfwfmError("libdfwfm lazy optim ABI mismatch")
+        for name, (res, args) in LAZY_LISTS_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        if L.dfwfm_lazy_lists_abi_version() != 1:
+            raise DfwfmError("libdfwfm lazy lists ABI mismatch")
         _lib = L
     return _lib
 

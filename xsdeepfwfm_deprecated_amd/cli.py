@@ -120,6 +120,10 @@ def get_parser():
            "batch touched, whichever optimizer runs (DeepFMs.lazy_tables, include/dfwfm_lazy_optim.h; with Adam the "
            "same as -lazy_adam).  Plain SGD and Adagrad without -l2 give the dense step's exact bits; momentum-SGD, "
            "RMSprop and any -l2 are NOT the dense optimizer: untouched rows get no decay and no L2")
+    a("-lazy_exchange", default=0, type=int, choices=[0, 1],
+      help="data-parallel training with -lazy_adam / -lazy_tables: the touched rows are those of the GLOBAL batch, "
+           "the union of the ranks' exchanged touched-row lists (DeepFMs.lazy_exchange, include/dfwfm_lazy_lists.h); "
+           "without it the lazy switches are refused under torch.distributed")
     return p
 
 
@@ -175,4 +179,5 @@ def get_model(cuda, feature_sizes, pars, dynamic_quantization=False, static_quan
     m.lr_schedule = getattr(pars, "lr_schedule", None)  # fit() raises if the fused Adam step is not the path
     m.fused_optimizer = bool(getattr(pars, "fused_optimizer", 0))  # fit() raises if the fused step is not the path
     m.lazy_tables = bool(getattr(pars, "lazy_tables", 0))  # fit() raises if the fused step is not the path
+    m.lazy_exchange = bool(getattr(pars, "lazy_exchange", 0))  # fit() raises without ranks or a lazy switch
     return m

@@ -7,6 +7,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <cmath>
 #include <string>
 #include <vector>
@@ -24,8 +25,10 @@
 #include "../../include/dfwfm_int8_tables.h"
 #include "../../include/dfwfm_optim.h"
 #include "../../include/dfwfm_lazy_optim.h"
+#include "../../include/dfwfm_lazy_lists.h"
 #include "dfwfm_optim.h"
 #include "dfwfm_lazy_optim.h"
+#include "dfwfm_lazy_lists.h"
 
 using namespace dfwfm;
 
@@ -2583,6 +2586,133 @@ int dfwfm_lazy_optim_step_dev_sched(const dfwfm_lazy_optim_table* t, int32_t n, 
   if (!sched_dev) return fail(DFWFM_ERR_INVALID_ARG, "null schedule block");
   return lazy_optim_step_dev_impl(t, n, xi, xi_stride, batch, hyper, reinterpret_cast<const LrSchedule*>(sched_dev),
                                   state_dev, stream);
+}
+
+// ---------------------------------------------------------------- include/dfwfm_lazy_lists.h
+int dfwfm_lazy_lists_abi_version(void) { return DFWFM_LAZY_LISTS_ABI_VERSION; }
+
+// the four calls of include/dfwfm_lazy_lists.h: `kind` kListsAdam (m, v: the moments) or an OptimKind (m: the state
+// array, v unused); with a schedule block (sched != null) the hyper-parameters' lr is unused
+static int lazy_lists_step_impl(int kind, const dfwfm_lazy_lists_span* spans, int32_t n_spans,
+                                const dfwfm_lazy_lists_list* lists, int32_t n_lists, float* grad, float* m, float* v,
+                                const AdamHyper& ah, const OptimHyper& oh, const LrSchedule* sched, void* state_dev,
+                                void* stream) {
+  static_assert(kListsSpans == DFWFM_LAZY_LISTS_SPANS_PER_LAUNCH && kListsLists == DFWFM_LAZY_LISTS_LISTS_PER_LAUNCH,
+                "lazy lists per-launch limits");
+  if (!state_dev) return fail(DFWFM_ERR_INVALID_ARG, "null state block");
+  if (n_spans < 0) return fail(DFWFM_ERR_INVALID_ARG, "negative span count");
+  if (n_lists < 0) return fail(DFWFM_ERR_INVALID_ARG, "negative list count");
+  if (n_spans > 0 && !spans) return fail(DFWFM_ERR_INVALID_ARG, "null span array");
+  if (n_lists > 0 && !lists) return fail(DFWFM_ERR_INVALID_ARG, "null list array");
+  if (!grad) return fail(DFWFM_ERR_INVALID_ARG, "null grad");
+  if (kind == kListsAdam && (!m || !v)) return fail(DFWFM_ERR_INVALID_ARG, "null exp_avg or exp_avg_sq");
+  if (kind != kListsAdam && kind != kOptSgd && !m) return fail(DFWFM_ERR_INVALID_ARG, "null state array (opt_state)");
+  std::vector<ListsSpan> sp((size_t)n_spans);
+  for (int i = 0; i < n_spans; ++i) {
+    const dfwfm_lazy_lists_span& x = spans[i];
+    if (!x.param || !x.stamp) return fail(DFWFM_ERR_INVALID_ARG, "lazy span %d: null pointer", i);
+    if (x.rows < 1 || x.width < 1) return fail(DFWFM_ERR_INVALID_ARG, "lazy span %d: rows and width must be >= 1", i);
+    if (x.offset < 0) return fail(DFWFM_ERR_INVALID_ARG, "lazy span %d: negative offset", i);
+    if (x.rows > (INT64_MAX - x.offset) / x.width)
+      return fail(DFWFM_ERR_INVALID_ARG, "lazy span %d: its end does not fit 63 bits", i);
+    sp[i] = ListsSpan{x.param, x.stamp, x.offset, x.offset + x.rows * (int64_t)x.width, x.width, i};
+  }
+  // sorted by offset: the kernel's search, and neighbours are the only candidates for an overlap
+  std::sort(sp.begin(), sp.end(), [](const ListsSpan& p, const ListsSpan& q) { return p.off < q.off; });
+  for (int i = 1; i < n_spans; ++i)
+    if (sp[i].off < sp[i - 1].end)
+      return fail(DFWFM_ERR_INVALID_ARG, "lazy span %d: overlapping offset (span %d reaches %lld, it starts at %lld)",
+                  sp[i].pad, sp[i - 1].pad, (long long)sp[i - 1].end, (long long)sp[i].off);
+  for (int i = 0; i < n_spans; ++i) sp[i].pad = 0;
+  for (int i = 0; i < n_lists; ++i) {
+    const dfwfm_lazy_lists_list& x = lists[i];
+    if (x.cap < 0) return fail(DFWFM_ERR_INVALID_ARG, "lazy list %d: cap < 0", i);
+    if (!x.dest || !x.count) return fail(DFWFM_ERR_INVALID_ARG, "lazy list %d: null pointer", i);
+    bool match = false;
+    for (int k = 0; k < n_spans && !match; ++k) match = sp[k].width == x.width;
+    if (x.width < 1 || !match) return fail(DFWFM_ERR_INVALID_ARG, "lazy list %d: width %d matches no span", i, x.width);
+    if ((x.cap + 255) / 256 > 0x3fffffff) return fail(DFWFM_ERR_UNSUPPORTED, "lazy list %d: too long", i);
+  }
+  ListsArgs a;
+  memset(&a, 0, sizeof a);
+  a.g = grad;
+  a.m = (kind == kOptSgd) ? nullptr : m;
+  a.v = (kind == kListsAdam) ? v : nullptr;
+  a.st = reinterpret_cast<AdamDevState*>(state_dev);
+  a.sched = sched;
+  a.ah = ah;
+  a.oh = oh;
+  // one launch per (piece of <= kListsSpans spans, piece of <= kListsLists lists); the call's last launch advances the
+  // device step counter (without a span or a list it is one empty workgroup)
+  const int ns = n_lists > 0 ? n_spans : 0;
+  for (int s0 = 0; s0 == 0 || s0 < ns; s0 += kListsSpans) {
+    a.ns = ns - s0 < kListsSpans ? ns - s0 : kListsSpans;
+    for (int k = 0; k < a.ns; ++k) a.sp[k] = sp[s0 + k];
+    const bool last_spans = s0 + kListsSpans >= ns;
+    const int nl = a.ns > 0 ? n_lists : 0;
+    int i = 0;
+    do {
+      int64_t blocks = 0;
+      a.nl = 0;
+      while (i < nl && a.nl < kListsLists) {
+        const int64_t nb = (lists[i].cap + 255) / 256;
+        if (a.nl > 0 && blocks + nb > 0x7fffffff) break;
+        a.ls[a.nl++] = ListsList{lists[i].dest, lists[i].count, lists[i].cap, lists[i].width, (int32_t)blocks};
+        blocks += nb;
+        ++i;
+      }
+      a.bump = (last_spans && i >= nl) ? 1 : 0;
+      a.nblocks = (int32_t)blocks;
+      hipError_t e = launch_lazy_lists(kind, a, (hipStream_t)stream);
+      if (e != hipSuccess) return hip_fail(e, "lazy lists launch");
+    } while (i < nl);
+  }
+  return DFWFM_OK;
+}
+
+int dfwfm_lazy_adam_lists_step_dev(const dfwfm_lazy_lists_span* spans, int32_t n_spans,
+                                   const dfwfm_lazy_lists_list* lists, int32_t n_lists, float* grad, float* exp_avg,
+                                   float* exp_avg_sq, double lr, double beta1, double beta2, double eps,
+                                   double weight_decay, void* state_dev, void* stream) {
+  return lazy_lists_step_impl(kListsAdam, spans, n_spans, lists, n_lists, grad, exp_avg, exp_avg_sq,
+                              AdamHyper{lr, beta1, beta2, eps, weight_decay}, OptimHyper{}, nullptr, state_dev, stream);
+}
+
+int dfwfm_lazy_adam_lists_step_dev_sched(const dfwfm_lazy_lists_span* spans, int32_t n_spans,
+                                         const dfwfm_lazy_lists_list* lists, int32_t n_lists, float* grad,
+                                         float* exp_avg, float* exp_avg_sq, const void* sched_dev, double beta1,
+                                         double beta2, double eps, double weight_decay, void* state_dev,
+                                         void* stream) {
+  if (!sched_dev) return fail(DFWFM_ERR_INVALID_ARG, "null schedule block");
+  return lazy_lists_step_impl(kListsAdam, spans, n_spans, lists, n_lists, grad, exp_avg, exp_avg_sq,
+                              AdamHyper{0.0, beta1, beta2, eps, weight_decay}, OptimHyper{},
+                              reinterpret_cast<const LrSchedule*>(sched_dev), state_dev, stream);
+}
+
+static int lazy_optim_lists_impl(const dfwfm_lazy_lists_span* spans, int32_t n_spans,
+                                 const dfwfm_lazy_lists_list* lists, int32_t n_lists, float* grad, float* opt_state,
+                                 const dfwfm_optim_hyper* hyper, const LrSchedule* sched, void* state_dev,
+                                 void* stream) {
+  int kind = 0;
+  if (int rc = optim_hyper_check(hyper, sched == nullptr, &kind)) return rc;
+  return lazy_lists_step_impl(kind, spans, n_spans, lists, n_lists, grad, opt_state, nullptr, AdamHyper{},
+                              OptimHyper{hyper->lr, hyper->weight_decay, hyper->momentum, hyper->alpha, hyper->eps},
+                              sched, state_dev, stream);
+}
+
+int dfwfm_lazy_optim_lists_step_dev(const dfwfm_lazy_lists_span* spans, int32_t n_spans,
+                                    const dfwfm_lazy_lists_list* lists, int32_t n_lists, float* grad, float* opt_state,
+                                    const dfwfm_optim_hyper* hyper, void* state_dev, void* stream) {
+  return lazy_optim_lists_impl(spans, n_spans, lists, n_lists, grad, opt_state, hyper, nullptr, state_dev, stream);
+}
+
+int dfwfm_lazy_optim_lists_step_dev_sched(const dfwfm_lazy_lists_span* spans, int32_t n_spans,
+                                          const dfwfm_lazy_lists_list* lists, int32_t n_lists, float* grad,
+                                          float* opt_state, const dfwfm_optim_hyper* hyper, const void* sched_dev,
+                                          void* state_dev, void* stream) {
+  if (!sched_dev) return fail(DFWFM_ERR_INVALID_ARG, "null schedule block");
+  return lazy_optim_lists_impl(spans, n_spans, lists, n_lists, grad, opt_state, hyper,
+                               reinterpret_cast<const LrSchedule*>(sched_dev), state_dev, stream);
 }
 
 int dfwfm_bce_grad(const float* z, const float* y, int64_t n, double denom, float* dz, float* loss_sum,

@@ -211,22 +211,43 @@ class FusedTrainStep:
     Plain SGD and Adagrad with weight_decay == 0 give the dense step's exact bits; momentum-SGD, RMSprop and any
     weight_decay != 0 are NOT the dense optimizer (an untouched row's buffer or square_avg does not decay, a
     momentum-SGD row is not moved by its buffer, an untouched row gets no L2).  Everything that is not a categorical
-    table stays on the dense update.  One process only."""
+    table stays on the dense update.  One process only, unless lazy_exchange is on.
+
+    lazy_exchange: lazy_table_adam / lazy_tables under data parallelism (``dist``).  "Touched" then means touched by
+    the GLOBAL batch: the union of every rank's exchanged touched-row list, which every rank holds after the sparse
+    exchange and whose rows _apply_sparse has just summed.  The tables' update (state_t) walks those lists
+    (include/dfwfm_lazy_lists.h: the same per-element arithmetic at the global step, a row several ranks touched
+    updated once, its gradient row zeroed), so the tables' region of the gradient buffer is not filled and no rank
+    streams every row; the other non-MLP tensors stay on `state`, the MLP on `state_b`, all three counters advancing
+    once per step.  Every replica walks the same lists over the same summed gradients, so replicas stay bit-identical.
+    It needs ``dist``, one of the two lazy switches and sparse_exchange (without it there are no lists): anything else
+    raises ValueError.  Off (the default): the lazy switches under ``dist`` raise NotImplementedError, as before."""
 
     def __init__(self, model, batch_size, lr=1e-3, weight_decay=0.0, betas=(0.9, 0.999), eps=None,
                  use_graph=True, dist=None, sparse_exchange=True, resident_inputs=False, max_graph_sets=8,
                  max_many_sets=2, deterministic=None, lazy_table_adam=False, lr_schedule=None,
-                 optimizer="adam", momentum=0.0, alpha=0.99, lazy_tables=False):
+                 optimizer="adam", momentum=0.0, alpha=0.99, lazy_tables=False, lazy_exchange=False):
         dev = model._device()
         if dev.type != "cuda":
             raise _lib.DfwfmError("FusedTrainStep runs only on a HIP device")
-        if lazy_tables and dist is not None:
+        if lazy_tables and dist is not None and not lazy_exchange:
             raise NotImplementedError("lazy_tables under data parallelism: the touched rows are the union of the "
-                                      "ranks' exchanged lists, which the lazy step does not read yet")
-        if lazy_table_adam and dist is not None:
+                                      "ranks' exchanged lists, which the lazy step reads only under "
+                                      "lazy_exchange=True (touched = touched by the global batch)")
+        if lazy_table_adam and dist is not None and not lazy_exchange:
             # the touched set of a data-parallel step is the union of every rank's exchanged lists (DESIGN.md section 9)
             raise NotImplementedError("lazy_table_adam under data parallelism: the touched rows are the union of the "
-                                      "ranks' exchanged lists, which the lazy step does not read yet")
+                                      "ranks' exchanged lists, which the lazy step reads only under "
+                                      "lazy_exchange=True (touched = touched by the global batch)")
+        if lazy_exchange:
+            if dist is None:
+                raise ValueError("lazy_exchange is the lazy table update under data parallelism: it needs dist")
+            if not (lazy_table_adam or lazy_tables):
+                raise ValueError("lazy_exchange needs lazy_table_adam or lazy_tables: it only says where their touched "
+                                 "rows come from")
+            if not sparse_exchange:
+                raise ValueError("lazy_exchange needs sparse_exchange: without the touched-row exchange there are no "
+                                 "lists to walk")
         if optimizer != "adam" and optimizer not in _lib.OPTIM_KINDS:
             raise ValueError(f"optimizer {optimizer!r}: one of 'adam', 'sgd', 'adag', 'rmsp'")
         if optimizer != "adam" and lazy_table_adam:
@@ -333,11 +354,14 @@ class FusedTrainStep:
         # lazy_table_adam / lazy_tables: the tables' update over the batch's touched rows only (no categorical table:
         # nothing to do)
         self.lazy = bool(lazy_table_adam or lazy_tables) and self.n_cat > 0
+        # lazy_exchange: the touched rows come from the exchanged lists (_setup_lazy_lists, once they are laid out)
+        self.lazy_lists = self.lazy and dist is not None
         if self.lazy:
-            if not self.split_adam:
+            if not (0 < self.n_cat < len(params)):
                 raise NotImplementedError(("lazy_table_adam" if lazy_table_adam else "lazy_tables") +
                                           ": a model whose only trainable parameters are tables")
-            self._setup_lazy(fields, params[:self.n_cat], views)
+            if not self.lazy_lists:
+                self._setup_lazy(fields, params[:self.n_cat], views)
         ptr = lambda t: None if t is None else views[id(t)].data_ptr()  # noqa: E731
         # sparse exchange: the backward scatters the categorical tables' gradients into a rank-local buffer (same
         # offsets as in self.grad, whose categorical region the lists fill); dfwfm_sparse_grads_local turns its
@@ -383,6 +407,8 @@ class FusedTrainStep:
         self.steps = 0
         if self.sparse:
             self._setup_sparse(fields, views)
+        if self.lazy_lists:
+            self._setup_lazy_lists(params[:self.n_cat])
 
     # -- touched-row exchange of the categorical tables' gradients (data parallelism) ------------------
     def _setup_sparse(self, fields, views):
@@ -475,6 +501,55 @@ class FusedTrainStep:
                     p.data_ptr(), g.data_ptr(), st, self.lazy_stamp[row0:].data_ptr(), rows, keys, c, width, col,
                     kind, 0)
             row0 += rows
+
+    def _setup_lazy_lists(self, tables):
+        """The descriptors of the list-driven lazy step (include/dfwfm_lazy_lists.h): one span per categorical table
+        (its tensor, its slice of the stamps, its offset in the flat buffers) and one list per (rank, family) of the
+        all-gathered receive buffer, in the order _apply_sparse adds them."""
+        self.lazy_stamp = torch.zeros(sum(int(p.shape[0]) for p in tables), dtype=torch.int32, device=self.dev)
+        self.ll_spans = (_lib.dfwfm_lazy_lists_span * len(tables))()
+        row0 = 0
+        for i, p in enumerate(tables):
+            rows = int(p.shape[0])
+            self.ll_spans[i] = _lib.dfwfm_lazy_lists_span(p.data_ptr(), self.lazy_stamp[row0:].data_ptr(),
+                                                          self.offs[i], rows, p.numel() // rows, 0)
+            row0 += rows
+        world = self.sp_recv.shape[0]
+        self.ll_lists = (_lib.dfwfm_lazy_lists_list * (world * len(self.sp_fams)))()
+        k = 0
+        for r in range(world):
+            rb = self.sp_recv[r].data_ptr()
+            for f in self.sp_fams:
+                self.ll_lists[k] = _lib.dfwfm_lazy_lists_list(rb + f["o_dest"], rb + f["o_cnt"], f["cap"], f["w"], 0)
+                k += 1
+
+    def _adam_tables_lists(self):
+        """The categorical tables' update on state_t over the rows the exchanged lists name (lazy_exchange), behind
+        _apply_sparse on the same stream: Adam, or the step's other optimizer, on the flat buffers."""
+        sp, ls = self.ll_spans, self.ll_lists
+        g, st = ctypes.c_void_p(self.grad.data_ptr()), ctypes.c_void_p(self.state_t.data_ptr())
+        if self.optimizer != "adam":
+            os_ = None if self.opt_state is None else ctypes.c_void_p(self.opt_state.data_ptr())
+            if self.sched is not None:
+                _lib.check(self.L.dfwfm_lazy_optim_lists_step_dev_sched(
+                    sp, len(sp), ls, len(ls), g, os_, ctypes.byref(self.hyper),
+                    ctypes.c_void_p(self.sched.data_ptr()), st, self._stream()),
+                    "dfwfm_lazy_optim_lists_step_dev_sched")
+                return
+            _lib.check(self.L.dfwfm_lazy_optim_lists_step_dev(sp, len(sp), ls, len(ls), g, os_,
+                                                              ctypes.byref(self.hyper), st, self._stream()),
+                       "dfwfm_lazy_optim_lists_step_dev")
+            return
+        m, v = ctypes.c_void_p(self.exp_avg.data_ptr()), ctypes.c_void_p(self.exp_avg_sq.data_ptr())
+        b1, b2 = self.betas
+        if self.sched is not None:
+            _lib.check(self.L.dfwfm_lazy_adam_lists_step_dev_sched(
+                sp, len(sp), ls, len(ls), g, m, v, ctypes.c_void_p(self.sched.data_ptr()), b1, b2, self.eps, self.wd,
+                st, self._stream()), "dfwfm_lazy_adam_lists_step_dev_sched")
+            return
+        _lib.check(self.L.dfwfm_lazy_adam_lists_step_dev(sp, len(sp), ls, len(ls), g, m, v, self.lr, b1, b2, self.eps,
+                                                         self.wd, st, self._stream()),
+                   "dfwfm_lazy_adam_lists_step_dev")
 
     def _adam_tables(self, n):
         """The categorical tables' update on state_t: every row (dense), or under lazy_table_adam / lazy_tables the
@@ -641,6 +716,12 @@ class FusedTrainStep:
         return self.dist is not None and self.n_bucket_a < self.grad.numel()
 
     def _adam_main(self):
+        if self.lazy_lists:
+            # lazy_exchange: the tables over the exchanged lists (state_t), the other non-MLP tensors dense (state; an
+            # empty list still advances the counter the dropout seed is read from)
+            self._adam_tables_lists()
+            self._adam_range(self.adam_rest, self.n_main - self.n_cat, self.state)
+            return
         if self.n_main:
             self._adam_range(self.adam, self.n_main, self.state)
 
@@ -1167,8 +1248,14 @@ def fit(model, Xi_train, Xv_train, y_train, Xi_valid=None, Xv_valid=None, y_vali
         # never train silently at another rate: the schedule exists on the fused step only
         raise ValueError("lr_schedule needs the fused training step: a module on a HIP device, "
                          "optimizer_type='adam', no teacher model and fused_fit on")
+    lazy_ex = bool(getattr(model, "lazy_exchange", False))
+    if lazy_ex and not fused:
+        # never select another path silently: the switch is the fused step's
+        raise ValueError("lazy_exchange needs the fused training step under torch.distributed, with lazy_table_adam "
+                         "or lazy_tables")
     trainer = FusedTrainStep(model, bs, lr=model.learning_rate, weight_decay=model.weight_decay,
                              dist=dist, lazy_table_adam=lazy, lr_schedule=sched, lazy_tables=lazy_tabs,
+                             **(dict(lazy_exchange=True) if lazy_ex else {}),
                              **({} if optimizer == "adam" else dict(optimizer=optimizer, momentum=model.momentum))) \
         if fused else None
     try:
