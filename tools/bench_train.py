@@ -3,6 +3,7 @@
     python tools/bench_train.py [--gpus N] [--steps K] [--warmup W] [--batch 4096] [--first-order lw|fwlw]
                                 [--lr-schedule 1:1e-4,2000:1e-3,200000:1e-4]
                                 [--optimizer adam|sgd|adag|rmsp] [--momentum M] [--lazy-tables]
+                                [--optimizer adag --rowwise-tables]
                                 [--exchange-world1 [--lazy-adam|--lazy-tables] --lazy-exchange [--apply-worlds 1,2,4,8]]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 tools/bench_train.py
 
@@ -58,6 +59,11 @@ def main():
                     help="fused, one rank: the categorical tables' update over the rows each batch touched only, "
                          "whichever --optimizer runs (FusedTrainStep(lazy_tables=True), include/dfwfm_lazy_optim.h; "
                          "with adam the same as --lazy-adam); composes with --momentum, --atomic and --lr-schedule")
+    ap.add_argument("--rowwise-tables", action="store_true",
+                    help="fused, one rank, --optimizer adag: row-wise Adagrad for the categorical tables, one "
+                         "accumulator per table row over the rows each batch touched "
+                         "(FusedTrainStep(rowwise_tables=True), include/dfwfm_rowwise_adagrad.h); composes with "
+                         "--atomic and --lr-schedule")
     ap.add_argument("--lazy-exchange", action="store_true",
                     help="fused, with --exchange-world1 or --gpus N and --lazy-adam / --lazy-tables: the lazy update "
                          "under data parallelism, over the exchanged touched-row lists "
@@ -86,6 +92,8 @@ def main():
     if a.lazy_exchange and (a.mode != "fused" or not (a.lazy_adam or a.lazy_tables)
                             or not (a.exchange_world1 or a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1)):
         ap.error("--lazy-exchange needs --mode fused, --lazy-adam or --lazy-tables, and --exchange-world1 or --gpus N")
+    if a.rowwise_tables and (a.mode != "fused" or a.optimizer != "adag"):
+        ap.error("--rowwise-tables needs --mode fused and --optimizer adag")
     from xsdeepfwfm_deprecated_amd.launch import spawn_ranks
     rc = spawn_ranks(a.gpus)  # before any HIP call
     if rc is not None:
@@ -141,6 +149,7 @@ def main():
                                  deterministic=not a.atomic, lazy_table_adam=a.lazy_adam, lr_schedule=schedule,
                                  **(dict(lazy_tables=True) if a.lazy_tables else {}),
                                  **(dict(lazy_exchange=True) if a.lazy_exchange else {}),
+                                 **(dict(rowwise_tables=True) if a.rowwise_tables else {}),
                                  **({} if a.optimizer == "adam" else dict(optimizer=a.optimizer, momentum=a.momentum)))
 
     def step(i):
@@ -194,12 +203,17 @@ def main():
            "lazy_adam": bool(trainer is not None and getattr(trainer, "lazy", False) and a.optimizer == "adam"),
            "lazy_tables": bool(trainer is not None and getattr(trainer, "lazy", False)),
            "lazy_exchange": bool(trainer is not None and getattr(trainer, "lazy_lists", False)),
+           "rowwise_tables": bool(trainer is not None and getattr(trainer, "rowwise", False)),
            "lr_schedule": schedule, "optimizer": a.optimizer, "momentum": a.momentum,
            "optimizer_bytes_per_param": opt_bytes,
            "final_loss_sum": round(float(loss.item()), 4)}
     if res["lazy_tables"]:
         # distinct rows the four resident batches touch per step, per table family (what the lazy step updates)
         res["touched_rows_per_step"] = touched_rows(model, [b[0] for b in batches])
+    if res["rowwise_tables"]:
+        # the tables' optimizer state: one float per row, against the element-wise Adagrad's one per element
+        res["table_state_bytes"] = {"rowwise": 4 * trainer.row_state.numel(),
+                                    "elementwise": 4 * sum(p.numel() for p in trainer.params[:trainer.n_cat])}
     if trainer is not None and getattr(trainer, "sparse", False):
         # touched-row lists all-gathered per step (fixed capacity: sum over tables of min(batch, rows))
         res["exchange"] = {"backend": torch.distributed.get_backend(), "packed_bytes_per_rank": trainer.sp_bytes,

@@ -183,6 +183,12 @@ class DeepFMs(nn.Module):
         # exchanged touched-row lists.  Off by default: fit() under torch.distributed with a lazy switch raises
         # NotImplementedError without it, and ValueError when it is set without a process group or a lazy switch
         self.lazy_exchange = False
+        # fit()'s fused Adagrad step trains the categorical tables with row-wise Adagrad
+        # (FusedTrainStep(rowwise_tables=True), include/dfwfm_rowwise_adagrad.h): one accumulator per table row, fed
+        # with the mean of the row's squared gradient, over the rows each batch touched -- a tenth of the tables' state
+        # at embedding_size 10, and NOT the reference's element-wise Adagrad.  Off by default; fit() raises ValueError
+        # when it is set and the fused step is not the path, optimizer_type is not 'adag' or fused_optimizer is off
+        self.rowwise_adagrad = False
         self._defer_index_check = 0    # >0 inside a batched caller: one flag read at its end, not per batch
         self._engine = None
 

@@ -124,6 +124,11 @@ def get_parser():
       help="data-parallel training with -lazy_adam / -lazy_tables: the touched rows are those of the GLOBAL batch, "
            "the union of the ranks' exchanged touched-row lists (DeepFMs.lazy_exchange, include/dfwfm_lazy_lists.h); "
            "without it the lazy switches are refused under torch.distributed")
+    a("-rowwise_adagrad", default=0, type=int, choices=[0, 1],
+      help="training on a HIP device with optimizer_type 'adag' and -fused_optimizer 1: the categorical tables are "
+           "trained with row-wise Adagrad, one accumulator per table row fed with the mean of the row's squared "
+           "gradient, over the rows each batch touched (DeepFMs.rowwise_adagrad, include/dfwfm_rowwise_adagrad.h); "
+           "NOT the reference's element-wise Adagrad; one process only")
     return p
 
 
@@ -180,4 +185,5 @@ def get_model(cuda, feature_sizes, pars, dynamic_quantization=False, static_quan
     m.fused_optimizer = bool(getattr(pars, "fused_optimizer", 0))  # fit() raises if the fused step is not the path
     m.lazy_tables = bool(getattr(pars, "lazy_tables", 0))  # fit() raises if the fused step is not the path
     m.lazy_exchange = bool(getattr(pars, "lazy_exchange", 0))  # fit() raises without ranks or a lazy switch
+    m.rowwise_adagrad = bool(getattr(pars, "rowwise_adagrad", 0))  # fit() raises off the fused Adagrad step
     return m

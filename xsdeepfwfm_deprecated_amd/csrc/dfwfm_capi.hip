@@ -26,9 +26,11 @@
 #include "../../include/dfwfm_optim.h"
 #include "../../include/dfwfm_lazy_optim.h"
 #include "../../include/dfwfm_lazy_lists.h"
+#include "../../include/dfwfm_rowwise_adagrad.h"
 #include "dfwfm_optim.h"
 #include "dfwfm_lazy_optim.h"
 #include "dfwfm_lazy_lists.h"
+#include "dfwfm_rowwise_adagrad.h"
 
 using namespace dfwfm;
 
@@ -2586,6 +2588,123 @@ int dfwfm_lazy_optim_step_dev_sched(const dfwfm_lazy_optim_table* t, int32_t n, 
   if (!sched_dev) return fail(DFWFM_ERR_INVALID_ARG, "null schedule block");
   return lazy_optim_step_dev_impl(t, n, xi, xi_stride, batch, hyper, reinterpret_cast<const LrSchedule*>(sched_dev),
                                   state_dev, stream);
+}
+
+// ---------------------------------------------------------------- include/dfwfm_rowwise_adagrad.h
+int dfwfm_rowwise_adagrad_abi_version(void) { return DFWFM_ROWWISE_ADAGRAD_ABI_VERSION; }
+
+// the hyper-parameters' checks of the row-wise calls: dfwfm_optim_step_dev's, and the kind is Adagrad
+static int rowwise_hyper_check(const dfwfm_optim_hyper* h, bool with_lr) {
+  int kind = 0;
+  if (int rc = optim_hyper_check(h, with_lr, &kind)) return rc;
+  if (h->kind != DFWFM_OPTIM_ADAGRAD)
+    return fail(DFWFM_ERR_INVALID_ARG, "row-wise Adagrad: optimizer kind %d is not DFWFM_OPTIM_ADAGRAD", h->kind);
+  return DFWFM_OK;
+}
+
+// dfwfm_rowwise_adagrad_step_dev and, with a schedule block (sched != null: hyper->lr unused),
+// dfwfm_rowwise_adagrad_step_dev_sched
+static int rowwise_adagrad_step_dev_impl(const dfwfm_rowwise_table* t, int32_t n, const int64_t* xi,
+                                         int64_t xi_stride, int64_t batch, const dfwfm_optim_hyper* hyper,
+                                         const LrSchedule* sched, void* state_dev, void* stream) {
+  if (int rc = rowwise_hyper_check(hyper, sched == nullptr)) return rc;
+  if (!state_dev) return fail(DFWFM_ERR_INVALID_ARG, "null state block");
+  if (n < 0) return fail(DFWFM_ERR_INVALID_ARG, "negative table count");
+  if (batch < 0) return fail(DFWFM_ERR_INVALID_ARG, "negative batch");
+  if (n > 0 && !t) return fail(DFWFM_ERR_INVALID_ARG, "null table array");
+  if (batch > 0 && n > 0 && (!xi || xi_stride < 1)) return fail(DFWFM_ERR_INVALID_ARG, "null xi or xi_stride < 1");
+  for (int i = 0; i < n; ++i) {
+    const dfwfm_rowwise_table& x = t[i];
+    if (!x.param || !x.grad || !x.stamp) return fail(DFWFM_ERR_INVALID_ARG, "rowwise table %d: null pointer", i);
+    if (!x.state) return fail(DFWFM_ERR_INVALID_ARG, "rowwise table %d: null state pointer", i);
+    if (x.rows < 1 || x.width < 1 || x.key_range < 1)
+      return fail(DFWFM_ERR_INVALID_ARG, "rowwise table %d: rows, width and key_range must be >= 1", i);
+    if (x.column < 0 || (batch > 0 && x.column >= xi_stride))
+      return fail(DFWFM_ERR_INVALID_ARG, "rowwise table %d: column %d outside xi's %lld", i, x.column,
+                  (long long)xi_stride);
+    if (x.kind != DFWFM_LAZY_PLAIN && x.kind != DFWFM_LAZY_QUOTIENT && x.kind != DFWFM_LAZY_REMAINDER)
+      return fail(DFWFM_ERR_INVALID_ARG, "rowwise table %d: kind %d", i, x.kind);
+    if (x.kind != DFWFM_LAZY_PLAIN && x.c < 1)
+      return fail(DFWFM_ERR_INVALID_ARG, "rowwise table %d: c < 1 on a QR kind", i);
+    // every key of [0, key_range) must land on a row of the table: the kernel indexes without a row count
+    const int64_t top = x.kind == DFWFM_LAZY_PLAIN ? x.key_range - 1
+                        : x.kind == DFWFM_LAZY_QUOTIENT ? (x.key_range - 1) / x.c
+                                                        : (x.c < x.key_range ? x.c : x.key_range) - 1;
+    if (top >= x.rows)
+      return fail(DFWFM_ERR_INVALID_ARG, "rowwise table %d: key range %lld reaches row %lld of %lld", i,
+                  (long long)x.key_range, (long long)top, (long long)x.rows);
+    if (lazy_blocks(x.width, batch) > 0x3fffffff)
+      return fail(DFWFM_ERR_UNSUPPORTED, "rowwise table %d: batch too large", i);
+  }
+  LazyOptimArgs a;
+  memset(&a, 0, sizeof a);
+  a.xi = xi;
+  a.xi_stride = xi_stride;
+  a.batch = batch;
+  a.st = reinterpret_cast<AdamDevState*>(state_dev);
+  a.sched = sched;
+  a.h = OptimHyper{hyper->lr, hyper->weight_decay, hyper->momentum, hyper->alpha, hyper->eps};
+  // the tables' launches (<= kLazyOptimList tables each); the last one advances the device step counter (without a
+  // table or a sample it is one empty workgroup)
+  LazyOptimList list;
+  memset(&list, 0, sizeof list);
+  const int nt = batch > 0 ? n : 0;
+  int64_t blocks = 0;
+  for (int i = 0; i <= nt; ++i) {
+    const bool last = i == nt;
+    const int64_t nb = last ? 0 : lazy_blocks(t[i].width, batch);
+    if (last || list.n == kLazyOptimList || blocks + nb > 0x7fffffff) {
+      a.bump = last ? 1 : 0;
+      a.nblocks = (int32_t)blocks;
+      hipError_t e = launch_rowwise_adagrad(list, a, (hipStream_t)stream);
+      if (e != hipSuccess) return hip_fail(e, "row-wise Adagrad launch");
+      list.n = 0;
+      blocks = 0;
+    }
+    if (last) break;
+    const dfwfm_rowwise_table& x = t[i];
+    LazyOptimTable& d = list.t[list.n];
+    d.p = x.param;
+    d.g = x.grad;
+    d.s = x.state;  // [rows]
+    d.stamp = x.stamp;
+    d.key_range = x.key_range;
+    d.c = x.c;
+    d.width = x.width;
+    d.column = x.column;
+    d.kind = x.kind;
+    d.block0 = (int32_t)blocks;
+    ++list.n;
+    blocks += nb;
+  }
+  return DFWFM_OK;
+}
+
+int dfwfm_rowwise_adagrad_step_dev(const dfwfm_rowwise_table* t, int32_t n, const int64_t* xi, int64_t xi_stride,
+                                   int64_t batch, const dfwfm_optim_hyper* hyper, void* state_dev, void* stream) {
+  return rowwise_adagrad_step_dev_impl(t, n, xi, xi_stride, batch, hyper, nullptr, state_dev, stream);
+}
+
+int dfwfm_rowwise_adagrad_step_dev_sched(const dfwfm_rowwise_table* t, int32_t n, const int64_t* xi,
+                                         int64_t xi_stride, int64_t batch, const dfwfm_optim_hyper* hyper,
+                                         const void* sched_dev, void* state_dev, void* stream) {
+  if (!sched_dev) return fail(DFWFM_ERR_INVALID_ARG, "null schedule block");
+  return rowwise_adagrad_step_dev_impl(t, n, xi, xi_stride, batch, hyper,
+                                       reinterpret_cast<const LrSchedule*>(sched_dev), state_dev, stream);
+}
+
+int dfwfm_rowwise_adagrad_row_ref(const dfwfm_optim_hyper* hyper, int32_t width, float* p, const float* g,
+                                  float* acc) {
+  if (int rc = rowwise_hyper_check(hyper, true)) return rc;
+  if (width < 1) return fail(DFWFM_ERR_INVALID_ARG, "width %d below 1", width);
+  if (!p || !g || !acc) return fail(DFWFM_ERR_INVALID_ARG, "null param, grad or accumulator");
+  const OptimCoef c = optim_coef(
+      1, OptimHyper{hyper->lr, hyper->weight_decay, hyper->momentum, hyper->alpha, hyper->eps}, hyper->lr);
+  float ss = 0.f;
+  for (int32_t e = 0; e < width; ++e) ss = rowwise_link(rowwise_grad(c, p[e], g[e]), ss);
+  const float std = rowwise_std(c, ss, width, *acc);
+  for (int32_t e = 0; e < width; ++e) p[e] = rowwise_elem(c, p[e], rowwise_grad(c, p[e], g[e]), std);
+  return DFWFM_OK;
 }
 
 // ---------------------------------------------------------------- include/dfwfm_lazy_lists.h

@@ -164,6 +164,20 @@ def check_exchange(world, nbytes, fams, max_bytes=None):
 
 
 
+def check_rowwise(optimizer, lazy_table_adam, dist):
+    """FusedTrainStep(rowwise_tables=True)'s refusals, which need no device: the optimizer, Adam's switch, and data
+    parallelism."""
+    if lazy_table_adam:
+        raise ValueError("rowwise_tables is row-wise Adagrad: it does not combine with lazy_table_adam (Adam's "
+                         "row-lazy step)")
+    if optimizer != "adag":
+        raise ValueError(f"rowwise_tables is row-wise Adagrad: it needs optimizer='adag', not {optimizer!r}")
+    if dist is not None:
+        raise NotImplementedError("rowwise_tables under data parallelism: the list-driven update walks flat buffers "
+                                  "with ONE offset per span for gradient and state (dfwfm_lazy_lists_span), and "
+                                  "row-wise state, one float per row, needs a state pointer per span")
+
+
 class FusedTrainStep:
     """One reference training step -- fit()'s inner-loop body (:619-637): zero_grad, forward,
     BCE-with-logits, backward, Adam(lr, weight_decay) -- as HIP launches on pre-built pointers, captured
@@ -221,15 +235,29 @@ class FusedTrainStep:
     streams every row; the other non-MLP tensors stay on `state`, the MLP on `state_b`, all three counters advancing
     once per step.  Every replica walks the same lists over the same summed gradients, so replicas stay bit-identical.
     It needs ``dist``, one of the two lazy switches and sparse_exchange (without it there are no lists): anything else
-    raises ValueError.  Off (the default): the lazy switches under ``dist`` raise NotImplementedError, as before."""
+    raises ValueError.  Off (the default): the lazy switches under ``dist`` raise NotImplementedError, as before.
+
+    rowwise_tables: row-wise Adagrad for the categorical tables (include/dfwfm_rowwise_adagrad.h: ONE accumulator per
+    table row, fed with the mean of the row's squared gradient -- the update large embedding tables are normally
+    trained with; NOT the reference's element-wise Adagrad).  It needs optimizer="adag" (else ValueError) and implies
+    the touched-row update: lazy_tables may be passed or not, with the same result; the tables' gradient region is not
+    filled per step.  ``row_state`` is that state, float32, one element per row of the categorical tables in table
+    order, zero at the start; ``opt_state`` then covers only the other parameters
+    (``opt_state.numel() == grad.numel() - n_tables``), which stay on the dense element-wise Adagrad.  Every path runs
+    it: eager, captured graph, step_many, resident inputs, lr_schedule / set_lr / set_lr_schedule, the deterministic
+    and the atomic scatter.  One process only: ``dist`` raises NotImplementedError.  Off (the default): ``row_state``
+    is None and everything is what it was."""
 
     def __init__(self, model, batch_size, lr=1e-3, weight_decay=0.0, betas=(0.9, 0.999), eps=None,
                  use_graph=True, dist=None, sparse_exchange=True, resident_inputs=False, max_graph_sets=8,
                  max_many_sets=2, deterministic=None, lazy_table_adam=False, lr_schedule=None,
-                 optimizer="adam", momentum=0.0, alpha=0.99, lazy_tables=False, lazy_exchange=False):
+                 optimizer="adam", momentum=0.0, alpha=0.99, lazy_tables=False, lazy_exchange=False,
+                 rowwise_tables=False):
         dev = model._device()
         if dev.type != "cuda":
             raise _lib.DfwfmError("FusedTrainStep runs only on a HIP device")
+        if rowwise_tables:
+            check_rowwise(optimizer, lazy_table_adam, dist)
         if lazy_tables and dist is not None and not lazy_exchange:
             raise NotImplementedError("lazy_tables under data parallelism: the touched rows are the union of the "
                                       "ranks' exchanged lists, which the lazy step reads only under "
@@ -299,13 +327,16 @@ class FusedTrainStep:
         self.n_bucket_a = next((offs[i] for i, p in enumerate(params) if id(p) in mlp_ids), total)
         self.sparse = dist is not None and bool(sparse_exchange) and self.n_tables > 0
         self.grad = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.exp_avg = self.exp_avg_sq = self.opt_state = None
+        self.exp_avg = self.exp_avg_sq = self.opt_state = self.row_state = None
+        # rowwise_tables: the tables' state is one float per row (row_state, _setup_lazy); opt_state starts behind them
+        self.rowwise = bool(rowwise_tables)
+        s0 = self.n_tables if self.rowwise else 0
         if optimizer == "adam":
             self.exp_avg = torch.zeros(total, dtype=torch.float32, device=dev)
             self.exp_avg_sq = torch.zeros(total, dtype=torch.float32, device=dev)
         elif _lib.OPTIM_KINDS[optimizer][2] or self.momentum != 0.0:
             # the kind's one state array (momentum buffer, sum, square_avg); plain SGD has none
-            self.opt_state = torch.zeros(total, dtype=torch.float32, device=dev)
+            self.opt_state = torch.zeros(total - s0, dtype=torch.float32, device=dev)
         self.state = torch.zeros(_lib.ADAM_STATE_BYTES // 8, dtype=torch.int64, device=dev)
         # under data parallelism Adam runs as two launches -- everything but the MLP
         # (state), the MLP weights and biases (state_b) -- so that the first can overlap the weight-gradient GEMM;
@@ -335,7 +366,8 @@ class FusedTrainStep:
                 m, v = (t[off:off + n].view_as(p) for t in (self.exp_avg, self.exp_avg_sq))
                 adam[i] = _lib.dfwfm_adam_tensor(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n)
             else:
-                st = None if self.opt_state is None else self.opt_state[off:off + n].data_ptr()
+                # (rowwise_tables: a table has no element-wise state, and no dense call ever takes its entry)
+                st = None if (self.opt_state is None or off < s0) else self.opt_state[off - s0:off - s0 + n].data_ptr()
                 adam[i] = _lib.dfwfm_optim_tensor(p.data_ptr(), g.data_ptr(), st, n)
         self.params, self.adam, self.n_adam = params, adam, len(params)
         self.offs = offs
@@ -353,12 +385,16 @@ class FusedTrainStep:
         self.split_adam = dist is None and 0 < self.n_cat < len(params)
         # lazy_table_adam / lazy_tables: the tables' update over the batch's touched rows only (no categorical table:
         # nothing to do)
-        self.lazy = bool(lazy_table_adam or lazy_tables) and self.n_cat > 0
+        self.lazy = bool(lazy_table_adam or lazy_tables or rowwise_tables) and self.n_cat > 0
         # lazy_exchange: the touched rows come from the exchanged lists (_setup_lazy_lists, once they are laid out)
         self.lazy_lists = self.lazy and dist is not None
+        if self.rowwise:
+            self.row_state = torch.zeros(sum(int(p.shape[0]) for p in params[:self.n_cat]), dtype=torch.float32,
+                                         device=dev)
         if self.lazy:
             if not (0 < self.n_cat < len(params)):
-                raise NotImplementedError(("lazy_table_adam" if lazy_table_adam else "lazy_tables") +
+                raise NotImplementedError(("rowwise_tables" if rowwise_tables else
+                                           "lazy_table_adam" if lazy_table_adam else "lazy_tables") +
                                           ": a model whose only trainable parameters are tables")
             if not self.lazy_lists:
                 self._setup_lazy(fields, params[:self.n_cat], views)
@@ -467,8 +503,10 @@ class FusedTrainStep:
 
     def _setup_lazy(self, fields, tables, views):
         """The table descriptors of dfwfm_lazy_adam_step_dev, or with another optimizer of dfwfm_lazy_optim_step_dev
-        (one state array, over opt_state; none for plain SGD): every categorical table with its xi column, its key
-        range (the forward's: a QR field accepts every key whose quotient row exists) and its slice of the stamps."""
+        (one state array, over opt_state; none for plain SGD), or under rowwise_tables of
+        dfwfm_rowwise_adagrad_step_dev (one state float per row, over row_state): every categorical table with its xi
+        column, its key range (the forward's: a QR field accepts every key whose quotient row exists) and its slice of
+        the stamps."""
         desc = {}
         for f in range(self.model.num, self.model.field_size):
             e2, e2r, e1, e1r = fields[f]
@@ -484,7 +522,9 @@ class FusedTrainStep:
                     desc[id(r)] = (f - self.model.num, keys, _lib.LAZY_REMAINDER, c)
         self.lazy_stamp = torch.zeros(sum(int(p.shape[0]) for p in tables), dtype=torch.int32, device=self.dev)
         adam = self.optimizer == "adam"
-        self.lazy_tables = ((_lib.dfwfm_lazy_adam_table if adam else _lib.dfwfm_lazy_optim_table) * len(tables))()
+        table_t = _lib.dfwfm_lazy_adam_table if adam else \
+            (_lib.dfwfm_rowwise_table if self.rowwise else _lib.dfwfm_lazy_optim_table)
+        self.lazy_tables = (table_t * len(tables))()
         row0 = 0
         for i, p in enumerate(tables):
             col, keys, kind, c = desc[id(p)]
@@ -495,6 +535,10 @@ class FusedTrainStep:
                 self.lazy_tables[i] = _lib.dfwfm_lazy_adam_table(
                     p.data_ptr(), g.data_ptr(), self.exp_avg[off:].data_ptr(), self.exp_avg_sq[off:].data_ptr(),
                     self.lazy_stamp[row0:].data_ptr(), rows, keys, c, width, col, kind, 0)
+            elif self.rowwise:
+                self.lazy_tables[i] = _lib.dfwfm_rowwise_table(
+                    p.data_ptr(), g.data_ptr(), self.row_state[row0:].data_ptr(), self.lazy_stamp[row0:].data_ptr(),
+                    rows, keys, c, width, col, kind, 0)
             else:
                 st = None if self.opt_state is None else self.opt_state[off:].data_ptr()
                 self.lazy_tables[i] = _lib.dfwfm_lazy_optim_table(
@@ -554,11 +598,23 @@ class FusedTrainStep:
     def _adam_tables(self, n):
         """The categorical tables' update on state_t: every row (dense), or under lazy_table_adam / lazy_tables the
         rows that the first n samples of the step's input buffer touch (Adam: include/dfwfm_lazy_adam.h; another
-        optimizer: include/dfwfm_lazy_optim.h)."""
+        optimizer: include/dfwfm_lazy_optim.h; rowwise_tables: include/dfwfm_rowwise_adagrad.h)."""
         if not self.lazy:
             self._adam_range(self.adam, self.n_cat, self.state_t)
             return
         xi = self._in[0]
+        if self.rowwise:
+            if self.sched is not None:
+                _lib.check(self.L.dfwfm_rowwise_adagrad_step_dev_sched(
+                    self.lazy_tables, self.n_cat, ctypes.c_void_p(xi.data_ptr()), xi.stride(0), n,
+                    ctypes.byref(self.hyper), ctypes.c_void_p(self.sched.data_ptr()),
+                    ctypes.c_void_p(self.state_t.data_ptr()), self._stream()), "dfwfm_rowwise_adagrad_step_dev_sched")
+                return
+            _lib.check(self.L.dfwfm_rowwise_adagrad_step_dev(
+                self.lazy_tables, self.n_cat, ctypes.c_void_p(xi.data_ptr()), xi.stride(0), n,
+                ctypes.byref(self.hyper), ctypes.c_void_p(self.state_t.data_ptr()), self._stream()),
+                "dfwfm_rowwise_adagrad_step_dev")
+            return
         if self.optimizer != "adam":
             if self.sched is not None:
                 _lib.check(self.L.dfwfm_lazy_optim_step_dev_sched(
@@ -1227,6 +1283,11 @@ def fit(model, Xi_train, Xv_train, y_train, Xi_valid=None, Xv_valid=None, y_vali
     if fused_opt and model.optimizer_type != "adam":
         optimizer = model.optimizer_type if model.optimizer_type in ("rmsp", "adag") else "sgd"
         fused = not teacher_model and getattr(model, "fused_fit", True) and device.type == "cuda"
+    rowwise = bool(getattr(model, "rowwise_adagrad", False))
+    if rowwise and not (fused and fused_opt and model.optimizer_type == "adag"):
+        # never train silently through another update: row-wise Adagrad exists on the fused step only
+        raise ValueError("rowwise_adagrad needs the fused training step with its Adagrad: a module on a HIP device, no "
+                         "teacher model, fused_fit on, optimizer_type='adag' and fused_optimizer on")
     if fused_opt and not fused:
         # never train silently through another path: the switch asks for the fused step
         raise ValueError("fused_optimizer needs the fused training step: a module on a HIP device, "
@@ -1256,6 +1317,7 @@ def fit(model, Xi_train, Xv_train, y_train, Xi_valid=None, Xv_valid=None, y_vali
     trainer = FusedTrainStep(model, bs, lr=model.learning_rate, weight_decay=model.weight_decay,
                              dist=dist, lazy_table_adam=lazy, lr_schedule=sched, lazy_tables=lazy_tabs,
                              **(dict(lazy_exchange=True) if lazy_ex else {}),
+                             **(dict(rowwise_tables=True) if rowwise else {}),
                              **({} if optimizer == "adam" else dict(optimizer=optimizer, momentum=model.momentum))) \
         if fused else None
     try:
