@@ -433,15 +433,18 @@ def _embeddings(case):
     return np.stack(out, 1)
 
 
-def deep_tower64(case, skip_x2_bwd=None, relu_from_prev_width=None, drop_last_row_of=None):
+def deep_tower64(case, skip_x2_bwd=None, relu_from_prev_width=None, drop_last_row_of=None, no_mask_bwd=False):
     """The deep tower's weight and bias gradients by hand in float64 (numpy), with a kernel's plausible slips:
-    skip_x2_bwd = h: the backward leaves out dropout layer h's x2; relu_from_prev_width = h: layer h's ReLU mask is
+    skip_x2_bwd = h: the backward leaves out dropout layer h's x2; no_mask_bwd: the backward applies no dropout at
+    all (masks and x2 in the forward only); relu_from_prev_width = h: layer h's ReLU mask is
     read from the flat [B, width] pre-activations with layer h - 1's width as the row stride; drop_last_row_of = h:
     dW_h without the batch's last row.  Without a slip it reproduces ref64 (asserted by the CPU leg)."""
     cfg, P = case.cfg, case.params
     H, B = cfg["h_depth"], len(case.xi)
     m = [np.ones((B, w)) for w in widths(cfg)] if case.masks is None else [2.0 * x.numpy() for x in case.masks]
     mb = [x if skip_x2_bwd != i else x / 2.0 for i, x in enumerate(m)]
+    if no_mask_bwd:
+        mb = [np.ones_like(x) for x in m]
     h = [_embeddings(case).reshape(B, -1) * m[0]]
     live = []
     for i in range(1, H + 1):
@@ -501,6 +504,7 @@ def mutations(case):
         H = cfg["h_depth"]
         if case.masks is not None:
             out["x2 of one dropout layer skipped in the backward"] = dict(g, **deep_tower64(case, skip_x2_bwd=H))
+            out["dropout in the forward only"] = dict(g, **deep_tower64(case, no_mask_bwd=True))
         out["ReLU mask taken at the previous layer's width"] = dict(g, **deep_tower64(case, relu_from_prev_width=1))
         out["last row of a ragged tile dropped from one dW"] = dict(g, **deep_tower64(case, drop_last_row_of=1))
     if cfg["qr_flag"] and cfg["qr_operation"] == "mult":

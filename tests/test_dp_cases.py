@@ -1,7 +1,10 @@
 """CPU: the shard plans of tests/dp_cases.py stand on their own -- the plans are fit()'s shards, the 129-row variant
 cases carry the witness's certificate, the float64 reference over the shards (normalised by the global batch) adds up
 to the global reference exactly, the host emulation of the touched-row exchange returns it and fails under each slip
-of the exchange, the rate-0 batches are finite, and eight ranks' slots of the packed buffer stay 16-byte aligned.
+of the exchange, the rate-0 batches are finite, and eight ranks' slots of the packed buffer stay 16-byte aligned.  With dropout on, the
+cases under the ranks' concatenated per-shard masks keep the certificate (and the saturated case its saturation), the
+float32 port returns the float64 bits, five slips of the mask rebuild and a backward without dropout each change what
+the GPU leg compares with, and training.rank_seed gives the ranks distinct seeds whose masks are uncorrelated.
 tests/test_gpu_dp_worlds.py holds the kernels and FusedTrainStep to the same reference."""
 import numpy as np
 import pytest
@@ -9,6 +12,7 @@ import torch
 
 import dp_cases as dc
 import exact_train_cases as xc
+from oracle import torch_port
 
 PLANS = [("A", k) for k in dc.A_PLANS] + [("B1", k) for k in dc.B1_PLANS]
 
@@ -136,3 +140,185 @@ def test_eight_slots_of_the_packed_buffer_stay_aligned(bs):
             assert a + n <= b
         for r in range(8):
             assert all((r * nbytes + o) % 16 == 0 for o, _ in spans)
+
+
+# =========================================================================== dropout under data parallelism
+A_DROP = [(m, p) for m in dc.A_MODELS for p in dc.A_PLANS]
+
+
+def _seeds(world):
+    return dc.SEEDS[:world]
+
+
+def _nonempty(sizes):
+    return sum(1 for s in sizes if s > 0)
+
+
+def test_shard_masks_are_the_ranks_own_local_rows():
+    """Per layer the ranks' masks one after the other, each over its local rows from 0 at its own seed and counter; an
+    empty shard adds no row; without a counter the seed itself (no step source attached)."""
+    cfg = xc.saturated().case.cfg
+    shards = dc.fit_shards(xc.SAT_B, 48, 4)  # 48 / 48 / 32 / 0
+    masks = dc.shard_masks(cfg, shards, _seeds(4), 2)
+    assert [tuple(m.shape) for m in masks] == [(xc.SAT_B, w) for w in xc.widths(cfg)]
+    for r, (lo, hi) in enumerate(shards):
+        own = torch_port.dropout_masks(torch_port.step_seed(dc.SEEDS[r], 2), 0.5, hi - lo, xc.widths(cfg))
+        assert all(torch.equal(m[lo:hi], o) for m, o in zip(masks, own)), r
+    raw = dc.shard_masks(cfg, shards[:1], _seeds(1), None)
+    assert all(torch.equal(m, o) for m, o in zip(raw, torch_port.dropout_masks(dc.SEEDS[0], 0.5, 48, xc.widths(cfg))))
+
+
+@pytest.mark.parametrize("plan", list(dc.B1_PLANS))
+def test_saturated_case_stays_exact_under_shard_masks(plan):
+    """Every B1 plan's concatenated per-rank masks at counter 2: the case stays saturated with its signs, the
+    certificate (p - 2^-6 g and the loss sum included) stays below 2^24 and sgd_ref is exact; the float32 port returns
+    the float64 bits forwards and with the batch reversed."""
+    world, _ = dc.B1_PLANS[plan]
+    sat0, sat = xc.saturated(), dc.b1_drop_case(plan, _seeds(world))
+    z, _ = xc.ref64(sat.case)
+    assert np.all(np.abs(z) >= xc.SAT_Z) and np.array_equal(z > 0, xc.ref64(sat0.case)[0] > 0)
+    assert sat.loss_sum == float(np.sum(np.maximum(z, 0.0) - z * sat.y)) and sat.loss_sum != sat0.loss_sum
+    cert = xc.saturated_certificate(sat)
+    worst = max(cert, key=cert.get)
+    print(f"sat-128 {plan} under shard masks: min |z| {np.abs(z).min():.0f}; worst {cert[worst] / xc.LIMIT:.3f} "
+          f"x 2^24 ({worst})")
+    assert all(v < xc.LIMIT for v in cert.values()), {k: v for k, v in cert.items() if v >= xc.LIMIT}
+    xc.sgd_ref(sat)  # asserts p - lr g is a float32
+    z32, g32 = xc.ref32(sat.case)
+    for reverse in (False, True):
+        zp, gp = xc.port32(sat.case, reverse)
+        assert np.array_equal(zp, z32) and not xc.differs(gp, g32), reverse
+
+
+@pytest.mark.parametrize("plan", dc.B1_DROP_PLANS)
+def test_rate0_logits_are_exact_under_each_ranks_masks(plan):
+    """The rate-0 steps' rows under each rank's masks at counters 0 and 1: the logits' bound over their quantum stays
+    below 2^24, and float32 arithmetic returns the float64 bits; the two counters' logits differ (the GPU leg can tell
+    the eager step's seed from the captured step's)."""
+    world, bs = dc.B1_PLANS[plan]
+    case = xc.saturated().case
+    q = xc.quanta(case)["logits"]
+    for rank in range(world):
+        z = []
+        for counter in (0, 1):
+            sub = dc.with_masks(dc.rows_of(case, dc.rate0_rows(rank, bs, xc.SAT_B)),
+                                dc.rank_masks(case.cfg, dc.SEEDS[rank], counter, bs))
+            assert xc.bounds(sub)["logits"] / q < xc.LIMIT
+            z.append(dc.rate0_logits(plan, rank, dc.SEEDS[rank], counter))
+            assert np.array_equal(xc.port32(sub)[0], z[-1]) and np.array_equal(xc.port32(sub, True)[0], z[-1])
+        assert not np.array_equal(z[0], z[1]), rank
+
+
+@pytest.mark.parametrize("model,plan", A_DROP)
+def test_129_row_cases_stay_exact_under_shard_masks(model, plan):
+    """Every A plan on every A model under its emulated ranks' masks (no step source): the certificate stays below
+    2^24, and the float32 port returns the float64 bits forwards and with the batch reversed."""
+    case = dc.a_drop_case(model, plan)
+    cert = xc.certificate(case)
+    worst = max(cert, key=cert.get)
+    print(f"{model}-129 {plan} under shard masks: worst {cert[worst]:.3g} ({worst}); limit 2^24 = {xc.LIMIT:.3g}")
+    assert all(v < xc.LIMIT for v in cert.values()), {k: v for k, v in cert.items() if v >= xc.LIMIT}
+    z32, g32 = xc.ref32(case)
+    for reverse in (False, True):
+        zp, gp = xc.port32(case, reverse)
+        assert np.array_equal(zp, z32) and not xc.differs(gp, g32), reverse
+    if plan != "w1":  # the shards' masks are not one process's on the whole batch
+        assert xc.differs(g32, xc.ref32(dc.a_case(model, True))[1])
+
+
+def _applies(mutation, sizes):
+    """Whether a slip of dc.MASK_MUTATIONS changes any mask: the global row and rank 0's seed only where a rank other
+    than rank 0 holds rows."""
+    return _nonempty(sizes[1:]) > 0 or mutation not in (dc.MASK_MUTATIONS[0], dc.MASK_MUTATIONS[3])
+
+
+def _sgd64(sat):
+    _, g = xc.ref64(sat.case)
+    return {k: p.astype(np.float64) - xc.SGD_LR * g[k] for k, p in sat.case.params.items()}
+
+
+@pytest.mark.parametrize("plan", dc.B1_DROP_PLANS)
+def test_each_mask_slip_changes_what_the_gloo_ranks_are_compared_with(plan):
+    """A reference that rebuilt the masks wrongly -- by the global row, at the counter before or after, from rank 0's
+    seed on every rank, at the next layer's index -- or left dropout out of the backward differs from the right one in
+    a float32 bit of some p - 2^-6 g, of some gradient and of the logits: what test_gpu_dp_worlds compares the ranks'
+    parameters and logits with would fail them."""
+    world, _ = dc.B1_PLANS[plan]
+    sat = dc.b1_drop_case(plan, _seeds(world))
+    (z, g), want = xc.ref64(sat.case), _sgd64(sat)
+    for mutation in dc.MASK_MUTATIONS:
+        mut = dc.b1_drop_case(plan, _seeds(world), 2, mutation)
+        zm, gm = xc.ref64(mut.case)
+        changed = xc.differs(_sgd64(mut), want)
+        print(f"B1 {plan}: {mutation}: {len(changed)} tensors of p - lr g differ, {int(np.sum(zm != z))} logits")
+        assert _applies(mutation, dc.B1_SIZES[plan])
+        assert changed and xc.differs(gm, g) and not np.array_equal(zm.astype(np.float32), z.astype(np.float32))
+        assert mut.loss_sum != sat.loss_sum
+    fwd_only = xc.mutations(sat.case)["dropout in the forward only"]
+    lr = {k: p.astype(np.float64) - xc.SGD_LR * fwd_only[k] for k, p in sat.case.params.items()}
+    assert xc.differs(fwd_only, g) and xc.differs(lr, want)
+
+
+@pytest.mark.parametrize("model,plan", A_DROP)
+def test_each_mask_slip_changes_what_the_emulated_ranks_are_compared_with(model, plan):
+    """The same slips on the 129-row models and the A plans (the 1-row and 0-row shards, QR, EmbeddingBag, fwlw): a
+    gradient bit and a logit change wherever the plan has what the slip needs (a second rank with rows)."""
+    case = dc.a_drop_case(model, plan)
+    z, g = xc.ref64(case)
+    for mutation in dc.MASK_MUTATIONS:
+        zm, gm = xc.ref64(dc.a_drop_case(model, plan, mutation))
+        changed = xc.differs(gm, g)
+        applies = _applies(mutation, dc.A_SIZES[plan])
+        assert bool(changed) == applies, (mutation, changed[:3])
+        assert (not np.array_equal(zm.astype(np.float32), z.astype(np.float32))) == applies, mutation
+    assert xc.differs(xc.mutations(case)["dropout in the forward only"], g)
+
+
+def test_hand_written_tower_is_the_reference_under_shard_masks():
+    """deep_tower64, in which the forward-only slip is made, reproduces ref64 under concatenated per-shard masks."""
+    for case in (dc.a_drop_case("base", "w4-tail"), dc.b1_drop_case("w4-middle", _seeds(4)).case):
+        _, g = xc.ref64(case)
+        for k, v in xc.deep_tower64(case).items():
+            assert np.array_equal(v, g[k]), k
+
+
+# ---- the ranks' seeds (training.rank_seed)
+BASES = (0, 1, 99, 1791095845, 2 ** 31 - 2, 2 ** 32 - 1)
+
+
+def test_rank_seed_keeps_rank_0_and_separates_the_ranks():
+    from xsdeepfwfm_deprecated_amd.training import rank_seed
+    for base in BASES:
+        seeds = [rank_seed(base, r) for r in range(8)]
+        assert seeds[0] == base and len(set(seeds)) == 8, (base, seeds)
+        assert all(isinstance(s, int) and 0 <= s < 2 ** 32 for s in seeds)
+        assert seeds == [rank_seed(base, r) for r in range(8)]  # a pure function
+    assert rank_seed(2 ** 32 + 5, 3) == rank_seed(5, 3)  # 32 bits, as dfwfm_train_forward takes the seed
+
+
+def _agreement(a, b):
+    """(fraction of equal entries, number of entries) of two lists of masks."""
+    n = sum(m.numel() for m in a)
+    return sum(int((x == y).sum()) for x, y in zip(a, b)) / n, n
+
+
+def test_rank_seeds_draw_uncorrelated_masks():
+    """Any two ranks' masks over 43 rows x the base model's widths agree on 0.5 +- 6 sigma of their entries (sigma =
+    0.5 / sqrt(n) for n independent fair bits; n = 43 x 1590 = 68 370: +- 0.0115), and so do one rank's masks at two
+    consecutive counters.  With one seed on every rank the agreement is 1."""
+    from xsdeepfwfm_deprecated_amd.training import rank_seed
+    cfg = xc.saturated().case.cfg
+    worst = 0.0
+    for base in BASES:
+        masks = [dc.rank_masks(cfg, rank_seed(base, r), 2, 43) for r in range(8)]
+        nxt = [dc.rank_masks(cfg, rank_seed(base, r), 3, 43) for r in range(8)]
+        pairs = [(masks[a], masks[b]) for a in range(8) for b in range(a + 1, 8)] + list(zip(masks, nxt))
+        for x, y in pairs:
+            frac, n = _agreement(x, y)
+            assert n == 43 * sum(xc.widths(cfg)) == 68370
+            worst = max(worst, abs(frac - 0.5))
+            assert abs(frac - 0.5) <= 6 * 0.5 / np.sqrt(n), (base, frac)
+        keep, n = _agreement(masks[0], [torch.ones_like(m) for m in masks[0]])
+        assert abs(keep - 0.5) <= 6 * 0.5 / np.sqrt(n)  # (and each mask keeps half)
+    print(f"worst |agreement - 0.5| = {worst:.4f}; bound {6 * 0.5 / np.sqrt(68370):.4f}")
+    assert _agreement(dc.rank_masks(cfg, 7, 2, 43), dc.rank_masks(cfg, 7, 2, 43))[0] == 1.0

@@ -134,7 +134,8 @@ def test_saturated_case_is_saturated():
 
 MUTATION_CASES = ("base-129", "base-129-drop", "qr_mult-37")
 WANTED = {"one sample dropped from a shared table row", "R instead of (R + R^T) / 2",
-          "x2 of one dropout layer skipped in the backward", "ReLU mask taken at the previous layer's width",
+          "x2 of one dropout layer skipped in the backward", "dropout in the forward only",
+          "ReLU mask taken at the previous layer's width",
           "last row of a ragged tile dropped from one dW", "remainder-table half of a QR mult gradient dropped"}
 
 

@@ -18,7 +18,8 @@ field whose every sample hits one of 3 rows, a field with all-distinct rows) and
 autograd and the whole C ABI.  On the saturated case (every |z| >= 128, B = denom = 128): dfwfm_bce_grad then the
 backward, dfwfm_backward_phases_bce whole and TILES then SPREAD, and FusedTrainStep with plain SGD -- eager and
 capture steps at rate 0 leave every parameter bit-identical, one replayed step at 2^-6 gives p - 2^-6 g bit for bit --
-deterministic on and off, lazy_tables, step_many.
+deterministic on and off, lazy_tables, step_many; and the same with dropout 0.5 on, step k under the masks of
+step_seed(t.seed, k - 1), rates 0, 0, 2^-6 on a device-resident schedule, step_many as two steps in one graph.
 
 A record of one session on an MI355X (not reproducible from the tree): all cases passed as the kernels stood, the
 file in 7 s.  A library built with three wrong-value slips put in on purpose -- dw_sum_kernel leaving out the last
@@ -363,6 +364,57 @@ def test_saturated_fused_sgd_step(gpu, mode):
     _assert_loss(mode, t.dlogit.cpu().numpy(), float(t.loss_sum.item()), sat)
     assert np.array_equal(t.out.cpu().numpy(), xc.ref32(case)[0]), (mode, "logits")
     want = xc.sgd_ref(sat)
+    for k, q in m.named_parameters():
+        got = q.detach().cpu().numpy()
+        assert np.array_equal(got, want[k]), (mode, k, int(np.sum(got != want[k])), "elements differ")
+    t.close()
+
+
+@pytest.mark.parametrize("mode", ["sorted", "atomic", "lazy_tables", "step_many"])
+def test_saturated_fused_sgd_step_with_dropout(gpu, mode):
+    """The same with the model's default, deep-tower dropout 0.5, on, the rates on a device-resident schedule (0, 0,
+    2^-6): step k draws its masks from step_seed(t.seed, k - 1), the trainer's device counter, in the forward and
+    again in the per-tile backward.  The eager step's logits are the reference's under counter 0's masks and the
+    captured step's under counter 1's (nothing moves at rate 0); after the third step every parameter is p - 2^-6 g
+    of the float64 reference under counter 2's masks bit for bit, with exact logits, dlogit and loss.  step_many
+    runs steps 2 and 3 as ONE graph over two resident batches.  The first time the dense non-Adam step runs with
+    dropout."""
+    import dp_cases as dc
+    from xsdeepfwfm_deprecated_amd.training import FusedTrainStep
+    sat0 = xc.saturated()
+    case = sat0.case
+    m = build(case.cfg, _writable(case.params), gpu, is_deep_dropout=True)
+    t = FusedTrainStep(m, xc.SAT_B, optimizer="sgd", momentum=0.0, weight_decay=0.0,
+                       lr_schedule=[(1, 0.0), (2, 0.0), (3, xc.SGD_LR), (4, 0.0)], deterministic=mode != "atomic",
+                       lazy_tables=mode == "lazy_tables", resident_inputs=mode == "step_many")
+    assert t.drop_train == 0.5
+    sats = [dc.with_masks(sat0, dc.rank_masks(case.cfg, t.seed, k, xc.SAT_B)) for k in range(3)]
+    assert max(xc.saturated_certificate(sats[2]).values()) < xc.LIMIT  # this seed's masks keep the witness's bound
+    z = [xc.ref32(s.case)[0] for s in sats]
+    assert not np.array_equal(z[0], z[1]) and not np.array_equal(z[1], z[2])
+    xi, xv, _ = _dev(gpu, case)
+    y = torch.from_numpy(sat0.y.copy()).to(gpu)
+    t.step(xi, xv, y)  # eager, counter 0
+    assert np.array_equal(t.out.cpu().numpy(), z[0]), (mode, "logits of the eager step")
+    if mode == "step_many":  # counters 1 and 2 in one graph, on two resident buffer sets
+        t.step_many([(xi, xv, y), (xi.clone(), xv.clone(), y.clone())])
+        torch.cuda.synchronize()
+        assert len(t._many_sets) == 1 and t.graphs is None
+    else:
+        t.step(xi, xv, y)  # captured, then replayed: counter 1
+        assert np.array_equal(t.out.cpu().numpy(), z[1]), (mode, "logits of the captured step")
+        for k, q in m.named_parameters():
+            assert np.array_equal(q.detach().cpu().numpy(), case.params[k]), (mode, k, "moved at rate 0")
+        t.loss_sum.zero_()  # (the trainer's loss sum runs over its steps)
+        t.step(xi, xv, y)  # replayed: counter 2
+        torch.cuda.synchronize()
+        assert t.graphs is not None and len(t._graph_sets) == 1
+        _assert_loss(mode, t.dlogit.cpu().numpy(), float(t.loss_sum.item()), sats[2])
+    assert int(t.state[0].item()) == 3
+    assert np.array_equal(t.out.cpu().numpy(), z[2]), (mode, "logits")
+    assert np.array_equal(t.dlogit.cpu().numpy(), sat0.case.dlogit), (mode, "dlogit")
+    want = xc.sgd_ref(sats[2])
+    assert xc.differs(want, xc.sgd_ref(sat0))  # (dropout moved the update)
     for k, q in m.named_parameters():
         got = q.detach().cpu().numpy()
         assert np.array_equal(got, want[k]), (mode, k, int(np.sum(got != want[k])), "elements differ")

@@ -43,6 +43,37 @@ def _grad_buffer(params, need, device):
     return flat, views
 
 
+def _mix32(x):
+    """murmur3's 32-bit finaliser (csrc/dfwfm_device.h mix32) on the host."""
+    x &= 0xFFFFFFFF
+    x ^= x >> 16
+    x = (x * 0x85EBCA6B) & 0xFFFFFFFF
+    x ^= x >> 13
+    x = (x * 0xC2B2AE35) & 0xFFFFFFFF
+    return x ^ (x >> 16)
+
+
+def rank_seed(base, rank):
+    """The dropout seed of data-parallel rank `rank`, in 32 bits as dfwfm_train_forward takes it.  Every rank seeds
+    torch's generator alike (DeepFMs.__init__: random_seed) and so draws the same `base`; the masks are a function of
+    (seed, layer, LOCAL row, column), so with one seed a global batch on W ranks would carry one mask pattern W times
+    over.  Rank 0 keeps `base` (one process and rank 0: the bits they always had); rank r > 0 gets base ^ mix32(r K1 +
+    K2), a murmur-finalised function of the rank: pairwise distinct over the ranks of any world below 2^32 - 2 (mix32
+    is a bijection with mix32(0) = 0; r -> r K1 + K2 = (r + 2) K1 is one too, K1 being odd, and 0 mod 2^32 only at
+    r = 2^32 - 2), and as unlike each other as the hash's outputs are."""
+    base, rank = int(base) & 0xFFFFFFFF, int(rank)
+    if rank == 0:
+        return base
+    return base ^ _mix32(rank * 0x9E3779B9 + 0x3C6EF372)
+
+
+def _dist_rank(dist=None):
+    """This process's rank under an initialised process group (`dist`: the torch.distributed module a trainer was
+    given), else 0."""
+    d = dist if dist is not None else torch.distributed
+    return int(d.get_rank()) if (d.is_available() and d.is_initialized()) else 0
+
+
 def train_forward(model, eng, xi, xv):
     """Logits with a HIP backward attached (reference forward in training mode, :285-469)."""
     if model.training and model.is_shallow_dropout and model.dropout_shallow and \
@@ -53,7 +84,8 @@ def train_forward(model, eng, xi, xv):
         p = float(model.dropout_deep[0])
         if any(float(d) != p for d in model.dropout_deep):
             raise NotImplementedError("dfwfm: per-layer dropout rates must be equal")
-    seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if p > 0 else 0
+    # (under an initialised process group every rank draws the same number: rank_seed separates the ranks' masks)
+    seed = rank_seed(int(torch.randint(0, 2 ** 31 - 1, (1,)).item()), _dist_rank()) if p > 0 else 0
     from . import torch_ops
     params = [q for q in model.parameters() if q.requires_grad]
     out, _ = torch.ops.dfwfm.forward(torch_ops.register(model), xi, xv, params, True, p, seed)
@@ -435,7 +467,11 @@ class FusedTrainStep:
         if model.use_deep and model.is_deep_dropout:
             self.drop_train = float(model.dropout_deep[0])
         self.drop = self.drop_train
+        # data parallelism: the ranks draw the same number here and index their masks by the local row, so each
+        # takes its own seed (rank_seed; rank 0 and one process keep the number drawn)
         self.seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+        if dist is not None:
+            self.seed = rank_seed(self.seed, dist.get_rank())
         _lib.check(self.L.dfwfm_set_step_source(self.eng.handle, ctypes.c_void_p(self.state.data_ptr())),
                    "dfwfm_set_step_source")
         self._attached = True
