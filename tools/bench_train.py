@@ -5,6 +5,8 @@
                                 [--optimizer adam|sgd|adag|rmsp] [--momentum M] [--lazy-tables]
                                 [--optimizer adag --rowwise-tables]
                                 [--exchange-world1 [--lazy-adam|--lazy-tables] --lazy-exchange [--apply-worlds 1,2,4,8]]
+                                [--exchange-world1 --optimizer adag --rowwise-tables --rowwise-exchange
+                                 [--apply-worlds 1,2,4,8]]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 tools/bench_train.py
 
 One step = the reference's fit() inner loop body (model/DeepFMs.py:619-637) on a resident synthetic
@@ -69,6 +71,10 @@ def main():
                          "under data parallelism, over the exchanged touched-row lists "
                          "(FusedTrainStep(lazy_exchange=True), include/dfwfm_lazy_lists.h); --apply-worlds then times "
                          "the lists update as well")
+    ap.add_argument("--rowwise-exchange", action="store_true",
+                    help="fused, with --rowwise-tables and --exchange-world1 or --gpus N: row-wise Adagrad under data "
+                         "parallelism, over the exchanged touched-row lists (FusedTrainStep(rowwise_exchange=True), "
+                         "include_dp/dfwfm_rowwise_lists.h); --apply-worlds then times the lists update as well")
     ap.add_argument("--lr-schedule", default=None, metavar="STEP:LR[,STEP:LR...]",
                     help="fused: the learning rate from a piecewise-linear schedule evaluated on the device every step "
                          "(FusedTrainStep(lr_schedule=...), e.g. \"1:1e-4,2000:1e-3,200000:1e-4\") instead of the "
@@ -94,6 +100,9 @@ def main():
         ap.error("--lazy-exchange needs --mode fused, --lazy-adam or --lazy-tables, and --exchange-world1 or --gpus N")
     if a.rowwise_tables and (a.mode != "fused" or a.optimizer != "adag"):
         ap.error("--rowwise-tables needs --mode fused and --optimizer adag")
+    if a.rowwise_exchange and (not a.rowwise_tables or not (
+            a.exchange_world1 or a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1)):
+        ap.error("--rowwise-exchange needs --rowwise-tables, and --exchange-world1 or --gpus N")
     from xsdeepfwfm_deprecated_amd.launch import spawn_ranks
     rc = spawn_ranks(a.gpus)  # before any HIP call
     if rc is not None:
@@ -150,6 +159,7 @@ def main():
                                  **(dict(lazy_tables=True) if a.lazy_tables else {}),
                                  **(dict(lazy_exchange=True) if a.lazy_exchange else {}),
                                  **(dict(rowwise_tables=True) if a.rowwise_tables else {}),
+                                 **(dict(rowwise_exchange=True) if a.rowwise_exchange else {}),
                                  **({} if a.optimizer == "adam" else dict(optimizer=a.optimizer, momentum=a.momentum)))
 
     def step(i):
@@ -204,6 +214,7 @@ def main():
            "lazy_tables": bool(trainer is not None and getattr(trainer, "lazy", False)),
            "lazy_exchange": bool(trainer is not None and getattr(trainer, "lazy_lists", False)),
            "rowwise_tables": bool(trainer is not None and getattr(trainer, "rowwise", False)),
+           "rowwise_exchange": bool(trainer is not None and getattr(trainer, "rowwise_exchange", False)),
            "lr_schedule": schedule, "optimizer": a.optimizer, "momentum": a.momentum,
            "optimizer_bytes_per_param": opt_bytes,
            "final_loss_sum": round(float(loss.item()), 4)}
@@ -305,13 +316,16 @@ def apply_bench(trainer, model, sizes, B, dev, worlds, reps=50):
 
 
 def lists_bench(trainer, recv, w, grad, dev, reps):
-    """The list-driven lazy update (include/dfwfm_lazy_lists.h) over W ranks' lists, graph-replayed on copies of the
-    flat buffers with a state block and stamps of its own (the trainer's are not touched): every replay is a fresh
-    step over the same rows.  Microseconds per call."""
+    """The list-driven lazy update (include/dfwfm_lazy_lists.h; under rowwise_exchange the row-wise one,
+    include_dp/dfwfm_rowwise_lists.h) over W ranks' lists, graph-replayed on copies of the flat buffers with a state block
+    and stamps of its own (the trainer's are not touched): every replay is a fresh step over the same rows.
+    Microseconds per call."""
     import ctypes
     from xsdeepfwfm_deprecated_amd import _lib
     L = _lib.lib()
     P = ctypes.c_void_p
+    if trainer.rowwise:
+        return rowwise_lists_bench(trainer, recv, w, grad, dev, reps)
     spans = (_lib.dfwfm_lazy_lists_span * len(trainer.ll_spans))()
     stamp = torch.zeros_like(trainer.lazy_stamp)
     keep, row0 = [], 0
@@ -341,6 +355,46 @@ def lists_bench(trainer, recv, w, grad, dev, reps):
             _lib.check(L.dfwfm_lazy_optim_lists_step_dev(spans, len(spans), lists, len(lists), P(grad.data_ptr()),
                                                          P(bufs[0].data_ptr()) if bufs else None,
                                                          ctypes.byref(trainer.hyper), P(state.data_ptr()), st), "lists")
+    for _ in range(3):
+        g.replay()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        g.replay()
+    e1.record()
+    torch.cuda.synchronize(dev)
+    return round(e0.elapsed_time(e1) * 1e3 / reps, 2)
+
+
+def rowwise_lists_bench(trainer, recv, w, grad, dev, reps):
+    """lists_bench for dfwfm_rowwise_adagrad_lists_step_dev: the spans carry a copy of row_state."""
+    import ctypes
+    from xsdeepfwfm_deprecated_amd import _lib
+    L = _lib.lib()
+    P = ctypes.c_void_p
+    spans = (_lib.dfwfm_rowwise_lists_span * len(trainer.ll_spans))()
+    stamp = torch.zeros_like(trainer.lazy_stamp)
+    acc = torch.zeros_like(trainer.row_state)
+    keep, row0 = [], 0
+    for i, sp in enumerate(trainer.ll_spans):
+        p = trainer.params[i].detach().clone()
+        keep.append(p)
+        spans[i] = _lib.dfwfm_rowwise_lists_span(p.data_ptr(), acc[row0:].data_ptr(), stamp[row0:].data_ptr(),
+                                                 sp.offset, sp.rows, sp.width, 0)
+        row0 += sp.rows
+    lists = (_lib.dfwfm_lazy_lists_list * (w * len(trainer.sp_fams)))()
+    for r in range(w):
+        rb = recv[r].data_ptr()
+        for k, f in enumerate(trainer.sp_fams):
+            lists[r * len(trainer.sp_fams) + k] = _lib.dfwfm_lazy_lists_list(rb + f["o_dest"], rb + f["o_cnt"],
+                                                                             f["cap"], f["w"], 0)
+    state = torch.zeros_like(trainer.state_t)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        st = P(torch.cuda.current_stream(dev).cuda_stream)  # the capture stream
+        _lib.check(L.dfwfm_rowwise_adagrad_lists_step_dev(spans, len(spans), lists, len(lists), P(grad.data_ptr()),
+                                                          ctypes.byref(trainer.hyper), P(state.data_ptr()), st),
+                   "rowwise lists")
     for _ in range(3):
         g.replay()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

@@ -189,6 +189,12 @@ class DeepFMs(nn.Module):
         # at embedding_size 10, and NOT the reference's element-wise Adagrad.  Off by default; fit() raises ValueError
         # when it is set and the fused step is not the path, optimizer_type is not 'adag' or fused_optimizer is off
         self.rowwise_adagrad = False
+        # rowwise_adagrad under data parallelism (FusedTrainStep(rowwise_exchange=True),
+        # include_dp/dfwfm_rowwise_lists.h): the rows of the GLOBAL batch, the union of the ranks' exchanged touched-row
+        # lists, get the row-wise update on every replica.  Off by default: fit() under torch.distributed with
+        # rowwise_adagrad raises NotImplementedError without it, and ValueError when it is set without a process
+        # group, without rowwise_adagrad or off the fused step
+        self.rowwise_exchange = False
         self._defer_index_check = 0    # >0 inside a batched caller: one flag read at its end, not per batch
         self._engine = None
 

@@ -26,7 +26,7 @@ LOAD_PATH = os.path.join(PKG_DIR, os.environ["DFWFM_LIB"]) if os.environ.get("DF
 SOURCES = ["dfwfm_kernels.hip", "dfwfm_fwd32.hip", "dfwfm_ftrain.hip", "dfwfm_train.hip", "dfwfm_prune.hip", "dfwfm_metrics.hip", "dfwfm_sparse.hip",
            "dfwfm_spmlp.hip", "dfwfm_serve.hip", "dfwfm_bf16.hip", "dfwfm_bf16_fused.hip", "dfwfm_int8.hip", "dfwfm_lazy_adam.hip",
            "dfwfm_optim.hip", "dfwfm_lazy_optim.hip", "dfwfm_lazy_lists.hip",
-           "dfwfm_rowwise_adagrad.hip",
+           "dfwfm_rowwise_adagrad.hip", "dfwfm_rowwise_lists.hip",
            "dfwfm_capi.hip"]
 # the forward / backward kernel templates are instantiated once per embedding size, each size in its own
 # translation unit (-DDFWFM_KD=<D>) so they compile in parallel; the plain object holds everything else
@@ -41,7 +41,7 @@ def _units():
         u += [(s, f"{os.path.splitext(s)[0]}_d{d}.o", [f"-DDFWFM_KD={d}"]) for d in EMB_SIZES]
     return u
 HEADERS = ["dfwfm_internal.h", "dfwfm_device.h", "dfwfm_fused_stage.h", "dfwfm_adam.h", "dfwfm_optim.h",
-           "dfwfm_lazy_optim.h", "dfwfm_lazy_lists.h", "dfwfm_rowwise_adagrad.h",
+           "dfwfm_lazy_optim.h", "dfwfm_lazy_lists.h", "dfwfm_rowwise_adagrad.h", "dfwfm_rowwise_lists.h",
            os.path.join("..", "..", "include", "dfwfm.h"),
            os.path.join("..", "..", "include", "dfwfm_serve.h"), os.path.join("..", "..", "include", "dfwfm_bf16.h"),
            os.path.join("..", "..", "include", "dfwfm_bf16_fused.h"), os.path.join("..", "..", "include", "dfwfm_fold.h"),
@@ -53,7 +53,8 @@ HEADERS = ["dfwfm_internal.h", "dfwfm_device.h", "dfwfm_fused_stage.h", "dfwfm_a
            os.path.join("..", "..", "include", "dfwfm_optim.h"),
            os.path.join("..", "..", "include", "dfwfm_lazy_optim.h"),
            os.path.join("..", "..", "include", "dfwfm_lazy_lists.h"),
-           os.path.join("..", "..", "include", "dfwfm_rowwise_adagrad.h")]
+           os.path.join("..", "..", "include", "dfwfm_rowwise_adagrad.h"),
+           os.path.join("..", "..", "include_dp", "dfwfm_rowwise_lists.h")]
 ARCH = os.environ.get("DFWFM_OFFLOAD_ARCH", "gfx950")
 CPU_PATH = os.path.join(PKG_DIR, "libdfwfm_cpu.so")
 CPU_SOURCES = ["dfwfm_cpu.cpp"]
@@ -148,6 +149,13 @@ class dfwfm_rowwise_table(ctypes.Structure):
 class dfwfm_lazy_lists_span(ctypes.Structure):
     _fields_ = [("param", ctypes.c_void_p), ("stamp", ctypes.c_void_p), ("offset", ctypes.c_int64),
                 ("rows", ctypes.c_int64), ("width", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class dfwfm_rowwise_lists_span(ctypes.Structure):
+    # dfwfm_lazy_lists_span plus `state`, the table's [rows] accumulators; `offset` indexes the gradient only
+    _fields_ = [("param", ctypes.c_void_p), ("state", ctypes.c_void_p), ("stamp", ctypes.c_void_p),
+                ("offset", ctypes.c_int64), ("rows", ctypes.c_int64), ("width", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
 
 
 class dfwfm_lazy_lists_list(ctypes.Structure):
@@ -361,6 +369,18 @@ ROWWISE_ADAGRAD_SIGNATURES = {
     "dfwfm_rowwise_adagrad_row_ref": (ctypes.c_int, [ctypes.POINTER(dfwfm_optim_hyper), ctypes.c_int32,
                                                      ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                                                      ctypes.POINTER(ctypes.c_float)]),
+}
+# the row-wise Adagrad step driven by exchanged touched-row lists (include_dp/dfwfm_rowwise_lists.h): same library, its
+# own header and ABI version
+ROWWISE_LISTS_SPANS_PER_LAUNCH, ROWWISE_LISTS_LISTS_PER_LAUNCH = 60, 24
+_ROW_LISTS = [ctypes.POINTER(dfwfm_rowwise_lists_span), ctypes.c_int32, ctypes.POINTER(dfwfm_lazy_lists_list),
+              ctypes.c_int32]
+ROWWISE_LISTS_SIGNATURES = {
+    "dfwfm_rowwise_lists_abi_version": (ctypes.c_int, []),
+    "dfwfm_rowwise_adagrad_lists_step_dev": (ctypes.c_int, _ROW_LISTS + [_P, ctypes.POINTER(dfwfm_optim_hyper), _P,
+                                                                         _P]),
+    "dfwfm_rowwise_adagrad_lists_step_dev_sched": (ctypes.c_int, _ROW_LISTS + [_P, ctypes.POINTER(dfwfm_optim_hyper),
+                                                                               _P, _P, _P]),
 }
 # FusedTrainStep's optimizer names (the reference's optimizer_type values) -> (kind, default eps, needs a state array
 # whatever the momentum)
@@ -662,6 +682,12 @@ def lib():
             fn.argtypes = args
         if L.dfwfm_rowwise_adagrad_abi_version() != 1:
             raise DfwfmError("libdfwfm row-wise Adagrad ABI mismatch")
+        for name, (res, args) in ROWWISE_LISTS_SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        if L.dfwfm_rowwise_lists_abi_version() != 1:
+            raise DfwfmError("libdfwfm row-wise lists ABI mismatch")
         _lib = L
     return _lib
 

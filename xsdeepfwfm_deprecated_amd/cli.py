@@ -128,7 +128,11 @@ def get_parser():
       help="training on a HIP device with optimizer_type 'adag' and -fused_optimizer 1: the categorical tables are "
            "trained with row-wise Adagrad, one accumulator per table row fed with the mean of the row's squared "
            "gradient, over the rows each batch touched (DeepFMs.rowwise_adagrad, include/dfwfm_rowwise_adagrad.h); "
-           "NOT the reference's element-wise Adagrad; one process only")
+           "NOT the reference's element-wise Adagrad; one process only, unless -rowwise_exchange 1")
+    a("-rowwise_exchange", default=0, type=int, choices=[0, 1],
+      help="data-parallel training with -rowwise_adagrad: the rows of the GLOBAL batch, the union of the ranks' "
+           "exchanged touched-row lists, get the row-wise update on every replica (DeepFMs.rowwise_exchange, "
+           "include_dp/dfwfm_rowwise_lists.h); without it -rowwise_adagrad is refused under torch.distributed")
     return p
 
 
@@ -186,4 +190,5 @@ def get_model(cuda, feature_sizes, pars, dynamic_quantization=False, static_quan
     m.lazy_tables = bool(getattr(pars, "lazy_tables", 0))  # fit() raises if the fused step is not the path
     m.lazy_exchange = bool(getattr(pars, "lazy_exchange", 0))  # fit() raises without ranks or a lazy switch
     m.rowwise_adagrad = bool(getattr(pars, "rowwise_adagrad", 0))  # fit() raises off the fused Adagrad step
+    m.rowwise_exchange = bool(getattr(pars, "rowwise_exchange", 0))  # fit() raises without ranks or rowwise_adagrad
     return m

@@ -27,10 +27,12 @@
 #include "../../include/dfwfm_lazy_optim.h"
 #include "../../include/dfwfm_lazy_lists.h"
 #include "../../include/dfwfm_rowwise_adagrad.h"
+#include "../../include_dp/dfwfm_rowwise_lists.h"
 #include "dfwfm_optim.h"
 #include "dfwfm_lazy_optim.h"
 #include "dfwfm_lazy_lists.h"
 #include "dfwfm_rowwise_adagrad.h"
+#include "dfwfm_rowwise_lists.h"
 
 using namespace dfwfm;
 
@@ -2832,6 +2834,104 @@ int dfwfm_lazy_optim_lists_step_dev_sched(const dfwfm_lazy_lists_span* spans, in
   if (!sched_dev) return fail(DFWFM_ERR_INVALID_ARG, "null schedule block");
   return lazy_optim_lists_impl(spans, n_spans, lists, n_lists, grad, opt_state, hyper,
                                reinterpret_cast<const LrSchedule*>(sched_dev), state_dev, stream);
+}
+
+// ---------------------------------------------------------------- include_dp/dfwfm_rowwise_lists.h
+int dfwfm_rowwise_lists_abi_version(void) { return DFWFM_ROWWISE_LISTS_ABI_VERSION; }
+
+// dfwfm_rowwise_adagrad_lists_step_dev and, with a schedule block (sched != null: hyper->lr unused), its _sched form:
+// lazy_lists_step_impl's checks and launch pieces with a state pointer per span, rowwise_hyper_check's hyper-parameters
+static int rowwise_lists_step_impl(const dfwfm_rowwise_lists_span* spans, int32_t n_spans,
+                                   const dfwfm_lazy_lists_list* lists, int32_t n_lists, float* grad,
+                                   const dfwfm_optim_hyper* hyper, const LrSchedule* sched, void* state_dev,
+                                   void* stream) {
+  static_assert(kRowListsSpans == DFWFM_ROWWISE_LISTS_SPANS_PER_LAUNCH &&
+                    kRowListsLists == DFWFM_ROWWISE_LISTS_LISTS_PER_LAUNCH,
+                "row-wise lists per-launch limits");
+  if (int rc = rowwise_hyper_check(hyper, sched == nullptr)) return rc;
+  if (!state_dev) return fail(DFWFM_ERR_INVALID_ARG, "null state block");
+  if (n_spans < 0) return fail(DFWFM_ERR_INVALID_ARG, "negative span count");
+  if (n_lists < 0) return fail(DFWFM_ERR_INVALID_ARG, "negative list count");
+  if (n_spans > 0 && !spans) return fail(DFWFM_ERR_INVALID_ARG, "null span array");
+  if (n_lists > 0 && !lists) return fail(DFWFM_ERR_INVALID_ARG, "null list array");
+  if (!grad) return fail(DFWFM_ERR_INVALID_ARG, "null grad");
+  std::vector<RowListsSpan> sp((size_t)n_spans);
+  for (int i = 0; i < n_spans; ++i) {
+    const dfwfm_rowwise_lists_span& x = spans[i];
+    if (!x.param || !x.stamp) return fail(DFWFM_ERR_INVALID_ARG, "rowwise span %d: null pointer", i);
+    if (!x.state) return fail(DFWFM_ERR_INVALID_ARG, "rowwise span %d: null state pointer", i);
+    if (x.rows < 1 || x.width < 1)
+      return fail(DFWFM_ERR_INVALID_ARG, "rowwise span %d: rows and width must be >= 1", i);
+    if (x.offset < 0) return fail(DFWFM_ERR_INVALID_ARG, "rowwise span %d: negative offset", i);
+    if (x.rows > (INT64_MAX - x.offset) / x.width)
+      return fail(DFWFM_ERR_INVALID_ARG, "rowwise span %d: its end does not fit 63 bits", i);
+    sp[i] = RowListsSpan{x.param, x.state, x.stamp, x.offset, x.offset + x.rows * (int64_t)x.width, x.width, i};
+  }
+  // sorted by offset: the kernel's search, and neighbours are the only candidates for an overlap
+  std::sort(sp.begin(), sp.end(), [](const RowListsSpan& p, const RowListsSpan& q) { return p.off < q.off; });
+  for (int i = 1; i < n_spans; ++i)
+    if (sp[i].off < sp[i - 1].end)
+      return fail(DFWFM_ERR_INVALID_ARG,
+                  "rowwise span %d: overlapping offset (span %d reaches %lld, it starts at %lld)", sp[i].pad,
+                  sp[i - 1].pad, (long long)sp[i - 1].end, (long long)sp[i].off);
+  for (int i = 0; i < n_spans; ++i) sp[i].pad = 0;
+  for (int i = 0; i < n_lists; ++i) {
+    const dfwfm_lazy_lists_list& x = lists[i];
+    if (x.cap < 0) return fail(DFWFM_ERR_INVALID_ARG, "rowwise list %d: cap < 0", i);
+    if (!x.dest || !x.count) return fail(DFWFM_ERR_INVALID_ARG, "rowwise list %d: null pointer", i);
+    bool match = false;
+    for (int k = 0; k < n_spans && !match; ++k) match = sp[k].width == x.width;
+    if (x.width < 1 || !match)
+      return fail(DFWFM_ERR_INVALID_ARG, "rowwise list %d: width %d matches no span", i, x.width);
+    if ((x.cap + 255) / 256 > 0x3fffffff) return fail(DFWFM_ERR_UNSUPPORTED, "rowwise list %d: too long", i);
+  }
+  RowListsArgs a;
+  memset(&a, 0, sizeof a);
+  a.g = grad;
+  a.st = reinterpret_cast<AdamDevState*>(state_dev);
+  a.sched = sched;
+  a.oh = OptimHyper{hyper->lr, hyper->weight_decay, hyper->momentum, hyper->alpha, hyper->eps};
+  // one launch per (piece of <= kRowListsSpans spans, piece of <= kRowListsLists lists); the call's last launch
+  // advances the device step counter (without a span or a list it is one empty workgroup)
+  const int ns = n_lists > 0 ? n_spans : 0;
+  for (int s0 = 0; s0 == 0 || s0 < ns; s0 += kRowListsSpans) {
+    a.ns = ns - s0 < kRowListsSpans ? ns - s0 : kRowListsSpans;
+    for (int k = 0; k < a.ns; ++k) a.sp[k] = sp[s0 + k];
+    const bool last_spans = s0 + kRowListsSpans >= ns;
+    const int nl = a.ns > 0 ? n_lists : 0;
+    int i = 0;
+    do {
+      int64_t blocks = 0;
+      a.nl = 0;
+      while (i < nl && a.nl < kRowListsLists) {
+        const int64_t nb = (lists[i].cap + 255) / 256;
+        if (a.nl > 0 && blocks + nb > 0x7fffffff) break;
+        a.ls[a.nl++] = ListsList{lists[i].dest, lists[i].count, lists[i].cap, lists[i].width, (int32_t)blocks};
+        blocks += nb;
+        ++i;
+      }
+      a.bump = (last_spans && i >= nl) ? 1 : 0;
+      a.nblocks = (int32_t)blocks;
+      hipError_t e = launch_rowwise_lists(a, (hipStream_t)stream);
+      if (e != hipSuccess) return hip_fail(e, "row-wise lists launch");
+    } while (i < nl);
+  }
+  return DFWFM_OK;
+}
+
+int dfwfm_rowwise_adagrad_lists_step_dev(const dfwfm_rowwise_lists_span* spans, int32_t n_spans,
+                                         const dfwfm_lazy_lists_list* lists, int32_t n_lists, float* grad,
+                                         const dfwfm_optim_hyper* hyper, void* state_dev, void* stream) {
+  return rowwise_lists_step_impl(spans, n_spans, lists, n_lists, grad, hyper, nullptr, state_dev, stream);
+}
+
+int dfwfm_rowwise_adagrad_lists_step_dev_sched(const dfwfm_rowwise_lists_span* spans, int32_t n_spans,
+                                               const dfwfm_lazy_lists_list* lists, int32_t n_lists, float* grad,
+                                               const dfwfm_optim_hyper* hyper, const void* sched_dev, void* state_dev,
+                                               void* stream) {
+  if (!sched_dev) return fail(DFWFM_ERR_INVALID_ARG, "null schedule block");
+  return rowwise_lists_step_impl(spans, n_spans, lists, n_lists, grad, hyper,
+                                 reinterpret_cast<const LrSchedule*>(sched_dev), state_dev, stream);
 }
 
 int dfwfm_bce_grad(const float* z, const float* y, int64_t n, double denom, float* dz, float* loss_sum,

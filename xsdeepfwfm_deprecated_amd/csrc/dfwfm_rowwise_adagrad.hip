@@ -32,59 +32,8 @@ __device__ __forceinline__ int32_t rowwise_stamp(int64_t step) {
   return (int32_t)(uint32_t)((uint64_t)(step - 1) % 0xffffffffull + 1ull);
 }
 
-// an owned row of width 1, by its owning lane
-__device__ __forceinline__ void rowwise_update_one(const OptimCoef& c, const LazyOptimTable& T, int64_t row) {
-  const float p = T.p[row];
-  const float gp = rowwise_grad(c, p, T.g[row]);
-  float acc = T.s[row];
-  const float std = rowwise_std(c, rowwise_link(gp, 0.f), 1, acc);
-  T.s[row] = acc;
-  T.p[row] = rowwise_elem(c, p, gp, std);
-  T.g[row] = 0.f;
-}
-
-// an owned row by the kLazyGroup lanes of one group, all of which call this with the same row (l: the lane's place
-// in its group).  The shuffles stay inside the group and run under group-uniform control flow only: a lane whose
-// element lies past the row's end still takes part, holding a value no link reads.
-__device__ __forceinline__ void rowwise_update_group(const OptimCoef& c, const LazyOptimTable& T, int64_t row, int l) {
-  const int W = T.width;
-  const int64_t r0 = row * W;
-  float acc = T.s[row];
-  float ss = 0.f, p0 = 0.f, g0 = 0.f, p1 = 0.f, g1 = 0.f;  // (p0, g0), (p1, g1): elements l and l + kLazyGroup
-  for (int base = 0; base < W; base += kLazyGroup) {
-    const int e = base + l;
-    float p = 0.f, gp = 0.f;
-    if (e < W) {
-      p = T.p[r0 + e];
-      gp = rowwise_grad(c, p, T.g[r0 + e]);
-    }
-    if (base == 0) {
-      p0 = p;
-      g0 = gp;
-    } else if (base == kLazyGroup) {
-      p1 = p;
-      g1 = gp;
-    }
-    const int m = W - base < kLazyGroup ? W - base : kLazyGroup;
-    for (int j = 0; j < m; ++j) ss = rowwise_link(__shfl(gp, j, kLazyGroup), ss);  // element base + j, in order
-  }
-  const float std = rowwise_std(c, ss, W, acc);
-  if (l == 0) T.s[row] = acc;
-  if (l < W) {
-    T.p[r0 + l] = rowwise_elem(c, p0, g0, std);
-    T.g[r0 + l] = 0.f;
-  }
-  if (l + kLazyGroup < W) {
-    T.p[r0 + l + kLazyGroup] = rowwise_elem(c, p1, g1, std);
-    T.g[r0 + l + kLazyGroup] = 0.f;
-  }
-  for (int e = 2 * kLazyGroup + l; e < W; e += kLazyGroup) {  // wider than two registers per lane: re-read
-    const float p = T.p[r0 + e];
-    const float gp = rowwise_grad(c, p, T.g[r0 + e]);
-    T.p[r0 + e] = rowwise_elem(c, p, gp, std);
-    T.g[r0 + e] = 0.f;
-  }
-}
+// (the two row functions, rowwise_update_one and rowwise_update_group, live in dfwfm_rowwise_adagrad.h: the
+// list-driven kernel calls the same ones)
 
 // SCHED: the first wave evaluates the schedule at the step (lr_schedule_value, dfwfm_adam.h) and its lane 0 forms the
 // scalars with that double in the place of a.h.lr; nothing else differs.
@@ -145,7 +94,7 @@ __global__ void __launch_bounds__(256) rowwise_adagrad_kernel(const LazyOptimLis
                       __hip_atomic_load(T.stamp + row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != stamp &&
                       atomicExch(T.stamp + row, stamp) != stamp;
     if (T.width == 1) {
-      if (mine) rowwise_update_one(c, T, row);
+      if (mine) rowwise_update_one(c, T.p + row, T.g + row, T.s + row);
       continue;  // (T is uniform over the workgroup)
     }
     const unsigned long long own = __ballot(mine);
@@ -153,8 +102,10 @@ __global__ void __launch_bounds__(256) rowwise_adagrad_kernel(const LazyOptimLis
     __syncthreads();
     const int n = __popcll(own);
     // (a group's lanes share k, so they enter and leave this loop together: the group's shuffles see all 16 of them)
-    for (int k = lane / kLazyGroup; k < n; k += 64 / kLazyGroup)
-      rowwise_update_group(c, T, s_rows[wave][k], lane % kLazyGroup);
+    for (int k = lane / kLazyGroup; k < n; k += 64 / kLazyGroup) {
+      const int64_t r = s_rows[wave][k];
+      rowwise_update_group(c, T.p + r * T.width, T.g + r * T.width, T.s + r, T.width, lane % kLazyGroup);
+    }
     __syncthreads();  // s_rows is rewritten by the next work block
   }
   if (a.bump && threadIdx.x == 0 && atomicAdd(&a.st->ticket, 1) == (int)gridDim.x - 1) optim_advance(a.st, c, s_step);

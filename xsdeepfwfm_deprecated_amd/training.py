@@ -196,18 +196,30 @@ def check_exchange(world, nbytes, fams, max_bytes=None):
 
 
 
-def check_rowwise(optimizer, lazy_table_adam, dist):
+def check_rowwise(optimizer, lazy_table_adam, dist, rowwise_exchange=False):
     """FusedTrainStep(rowwise_tables=True)'s refusals, which need no device: the optimizer, Adam's switch, and data
-    parallelism."""
+    parallelism without rowwise_exchange (with it the tables walk the exchanged lists: include_dp/dfwfm_rowwise_lists.h)."""
     if lazy_table_adam:
         raise ValueError("rowwise_tables is row-wise Adagrad: it does not combine with lazy_table_adam (Adam's "
                          "row-lazy step)")
     if optimizer != "adag":
         raise ValueError(f"rowwise_tables is row-wise Adagrad: it needs optimizer='adag', not {optimizer!r}")
-    if dist is not None:
+    if dist is not None and not rowwise_exchange:
         raise NotImplementedError("rowwise_tables under data parallelism: the list-driven update walks flat buffers "
                                   "with ONE offset per span for gradient and state (dfwfm_lazy_lists_span), and "
                                   "row-wise state, one float per row, needs a state pointer per span")
+
+
+def check_rowwise_exchange(rowwise_tables, dist, sparse_exchange):
+    """FusedTrainStep(rowwise_exchange=True)'s refusals, which need no device: it is rowwise_tables under data
+    parallelism over the exchanged touched-row lists, so it needs all three."""
+    if dist is None:
+        raise ValueError("rowwise_exchange is row-wise Adagrad under data parallelism: it needs dist")
+    if not rowwise_tables:
+        raise ValueError("rowwise_exchange needs rowwise_tables: it only says where their touched rows come from")
+    if not sparse_exchange:
+        raise ValueError("rowwise_exchange needs sparse_exchange: without the touched-row exchange there are no "
+                         "lists to walk")
 
 
 class FusedTrainStep:
@@ -277,20 +289,31 @@ class FusedTrainStep:
     order, zero at the start; ``opt_state`` then covers only the other parameters
     (``opt_state.numel() == grad.numel() - n_tables``), which stay on the dense element-wise Adagrad.  Every path runs
     it: eager, captured graph, step_many, resident inputs, lr_schedule / set_lr / set_lr_schedule, the deterministic
-    and the atomic scatter.  One process only: ``dist`` raises NotImplementedError.  Off (the default): ``row_state``
-    is None and everything is what it was."""
+    and the atomic scatter.  One process only, unless rowwise_exchange is on: ``dist`` alone raises
+    NotImplementedError.  Off (the default): ``row_state`` is None and everything is what it was.
+
+    rowwise_exchange: rowwise_tables under data parallelism (``dist``).  As under lazy_exchange, "touched" means touched
+    by the GLOBAL batch: the tables' update (state_t) walks the exchanged lists behind _apply_sparse on the same stream
+    (include_dp/dfwfm_rowwise_lists.h: the claim of the list-driven lazy step joined with the row arithmetic of
+    dfwfm_rowwise_adagrad_row_ref, a state pointer per table), eagerly, in the graph pieces around a gloo exchange
+    and inside the RCCL-in-graph capture alike.  ``row_state`` and ``opt_state`` are laid out as on one process; every
+    replica walks the same lists over the same summed gradients, so replicas stay bit-identical, ``row_state``
+    included.  lazy_tables may be passed or not, with the same result.  It needs ``dist``, rowwise_tables and
+    sparse_exchange: anything else raises ValueError.  Off (the default): nothing changes."""
 
     def __init__(self, model, batch_size, lr=1e-3, weight_decay=0.0, betas=(0.9, 0.999), eps=None,
                  use_graph=True, dist=None, sparse_exchange=True, resident_inputs=False, max_graph_sets=8,
                  max_many_sets=2, deterministic=None, lazy_table_adam=False, lr_schedule=None,
                  optimizer="adam", momentum=0.0, alpha=0.99, lazy_tables=False, lazy_exchange=False,
-                 rowwise_tables=False):
+                 rowwise_tables=False, rowwise_exchange=False):
         dev = model._device()
         if dev.type != "cuda":
             raise _lib.DfwfmError("FusedTrainStep runs only on a HIP device")
+        if rowwise_exchange:
+            check_rowwise_exchange(rowwise_tables, dist, sparse_exchange)
         if rowwise_tables:
-            check_rowwise(optimizer, lazy_table_adam, dist)
-        if lazy_tables and dist is not None and not lazy_exchange:
+            check_rowwise(optimizer, lazy_table_adam, dist, rowwise_exchange)
+        if lazy_tables and dist is not None and not (lazy_exchange or rowwise_exchange):
             raise NotImplementedError("lazy_tables under data parallelism: the touched rows are the union of the "
                                       "ranks' exchanged lists, which the lazy step reads only under "
                                       "lazy_exchange=True (touched = touched by the global batch)")
@@ -362,6 +385,7 @@ class FusedTrainStep:
         self.exp_avg = self.exp_avg_sq = self.opt_state = self.row_state = None
         # rowwise_tables: the tables' state is one float per row (row_state, _setup_lazy); opt_state starts behind them
         self.rowwise = bool(rowwise_tables)
+        self.rowwise_exchange = bool(rowwise_exchange)
         s0 = self.n_tables if self.rowwise else 0
         if optimizer == "adam":
             self.exp_avg = torch.zeros(total, dtype=torch.float32, device=dev)
@@ -585,14 +609,22 @@ class FusedTrainStep:
     def _setup_lazy_lists(self, tables):
         """The descriptors of the list-driven lazy step (include/dfwfm_lazy_lists.h): one span per categorical table
         (its tensor, its slice of the stamps, its offset in the flat buffers) and one list per (rank, family) of the
-        all-gathered receive buffer, in the order _apply_sparse adds them."""
+        all-gathered receive buffer, in the order _apply_sparse adds them.  Under rowwise_exchange the spans are those
+        of include_dp/dfwfm_rowwise_lists.h: the offset is the gradient's alone, and the table's slice of row_state rides
+        along."""
         self.lazy_stamp = torch.zeros(sum(int(p.shape[0]) for p in tables), dtype=torch.int32, device=self.dev)
-        self.ll_spans = (_lib.dfwfm_lazy_lists_span * len(tables))()
+        span_t = _lib.dfwfm_rowwise_lists_span if self.rowwise else _lib.dfwfm_lazy_lists_span
+        self.ll_spans = (span_t * len(tables))()
         row0 = 0
         for i, p in enumerate(tables):
             rows = int(p.shape[0])
-            self.ll_spans[i] = _lib.dfwfm_lazy_lists_span(p.data_ptr(), self.lazy_stamp[row0:].data_ptr(),
-                                                          self.offs[i], rows, p.numel() // rows, 0)
+            if self.rowwise:
+                self.ll_spans[i] = _lib.dfwfm_rowwise_lists_span(
+                    p.data_ptr(), self.row_state[row0:].data_ptr(), self.lazy_stamp[row0:].data_ptr(), self.offs[i],
+                    rows, p.numel() // rows, 0)
+            else:
+                self.ll_spans[i] = _lib.dfwfm_lazy_lists_span(p.data_ptr(), self.lazy_stamp[row0:].data_ptr(),
+                                                              self.offs[i], rows, p.numel() // rows, 0)
             row0 += rows
         world = self.sp_recv.shape[0]
         self.ll_lists = (_lib.dfwfm_lazy_lists_list * (world * len(self.sp_fams)))()
@@ -605,9 +637,20 @@ class FusedTrainStep:
 
     def _adam_tables_lists(self):
         """The categorical tables' update on state_t over the rows the exchanged lists name (lazy_exchange), behind
-        _apply_sparse on the same stream: Adam, or the step's other optimizer, on the flat buffers."""
+        _apply_sparse on the same stream: Adam, or the step's other optimizer, on the flat buffers; under
+        rowwise_exchange row-wise Adagrad on the spans' own accumulators."""
         sp, ls = self.ll_spans, self.ll_lists
         g, st = ctypes.c_void_p(self.grad.data_ptr()), ctypes.c_void_p(self.state_t.data_ptr())
+        if self.rowwise:
+            if self.sched is not None:
+                _lib.check(self.L.dfwfm_rowwise_adagrad_lists_step_dev_sched(
+                    sp, len(sp), ls, len(ls), g, ctypes.byref(self.hyper), ctypes.c_void_p(self.sched.data_ptr()), st,
+                    self._stream()), "dfwfm_rowwise_adagrad_lists_step_dev_sched")
+                return
+            _lib.check(self.L.dfwfm_rowwise_adagrad_lists_step_dev(sp, len(sp), ls, len(ls), g,
+                                                                   ctypes.byref(self.hyper), st, self._stream()),
+                       "dfwfm_rowwise_adagrad_lists_step_dev")
+            return
         if self.optimizer != "adam":
             os_ = None if self.opt_state is None else ctypes.c_void_p(self.opt_state.data_ptr())
             if self.sched is not None:
@@ -1350,10 +1393,16 @@ def fit(model, Xi_train, Xv_train, y_train, Xi_valid=None, Xv_valid=None, y_vali
         # never select another path silently: the switch is the fused step's
         raise ValueError("lazy_exchange needs the fused training step under torch.distributed, with lazy_table_adam "
                          "or lazy_tables")
+    row_ex = bool(getattr(model, "rowwise_exchange", False))
+    if row_ex and not (fused and rowwise and dist):
+        # never select another path silently: the switch is the fused row-wise step's under data parallelism
+        raise ValueError("rowwise_exchange needs the fused training step under torch.distributed, with "
+                         "rowwise_adagrad")
     trainer = FusedTrainStep(model, bs, lr=model.learning_rate, weight_decay=model.weight_decay,
                              dist=dist, lazy_table_adam=lazy, lr_schedule=sched, lazy_tables=lazy_tabs,
                              **(dict(lazy_exchange=True) if lazy_ex else {}),
                              **(dict(rowwise_tables=True) if rowwise else {}),
+                             **(dict(rowwise_exchange=True) if row_ex else {}),
                              **({} if optimizer == "adam" else dict(optimizer=optimizer, momentum=model.momentum))) \
         if fused else None
     try:
